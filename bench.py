@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — OMGSR single-mid-timestep SR throughput on MI355X (see BASELINE.json / BASELINE.md).
 
-    python bench.py --gpus N --steps K --warmup W [--workload s1024|s512|f1024] [--batch B] [--weight-dtype fp32|fp16|bf16]
+    python bench.py --gpus N --steps K --warmup W [--workload s1024|s512|f1024] [--batch B] [--weight-dtype fp32|fp16|bf16] [--dump-outputs DIR]
 
 One process per GPU. With the torchrun env (RANK / WORLD_SIZE ...) this process IS a rank; without it and N > 1 the
 parent launches `python -m torch.distributed.run --nproc-per-node N ...` on itself as a child BEFORE anything touches the
@@ -51,6 +51,8 @@ IGEMM_VARIANTS = {1: "igemm_kernel", 2: "igemm_dma_kernel", 3: "igemm_halo_kerne
                   13: "igemm_halo_kernel<fp6>", 14: "igemm_halo_multi_kernel<fp6>", 15: "igemm_halo_multi_kernel<fp6>(split-K)+splitk_reduce_kernel",
                   16: "igemm_halo_kernel<TAPS=4>", 17: "igemm_halo_multi_kernel<TAPS=4>"}       # 16 / 17: the phase form with fp6 correction chunks (named by its form, like rocprofv3's rows)
 FP6_VARIANTS = (13, 14, 15, 16, 17)       # correction chunks as fp6: 8 MFMA passes per 64 channels where fp8 takes 16 - 3/4 of the fp8 form's matrix-pipe time
+DUMP_MAX_BYTES = 64 * 10**6               # --dump-outputs: most bytes one run writes
+DUMP_SAMPLE_SEED = 20240                  # --dump-outputs: seed of the row sample taken from an output above that
 
 
 def parse(argv=None):
@@ -77,7 +79,17 @@ def parse(argv=None):
                     help="where the full record goes (per-kernel tables, every tier, f1024 / latency records); the stdout line stays compact")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="exercise the N-rank launch / RCCL-shaped broadcast / reporting path on CPU (gloo, reduced models, no kernels)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy in float32, "
+                         f"at most {DUMP_MAX_BYTES // 10**6} MB in all (a larger output is written as a fixed, seeded sample of its rows); "
+                         "the inputs are seeded, so two builds run with the same arguments can be compared output for output "
+                         "(bench_outputs/ is git-ignored for this)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.dry_run_cpu:
+        ap.error("--dump-outputs needs the GPU path (the CPU dry run computes no outputs)")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -287,6 +299,8 @@ def main():
     fastest = D.min_over_ranks(elapsed, device)
     elapsed = D.max_over_ranks(elapsed, device)
     ranks_seen = D.world_size_seen()            # a collective: every rank takes part
+    if rank == 0 and args.dump_outputs:         # what the caller of the timed path received from its last step
+        dump_output(args.dump_outputs, "image", out)
     images = B * world * args.steps
     value = images / elapsed
 
@@ -485,6 +499,25 @@ def make_step(pipe, family, inp, tile, overlap):
     if family == "S":
         return lambda: pipe(inp["lq"], inp["prompt"], tile, overlap)[0]
     return lambda: pipe(inp["lq"], inp["prompt"], inp["pooled"], inp["text_ids"], inp["image_ids"], tile, overlap)[0]
+
+
+def dump_output(out_dir, name, t):
+    """--dump-outputs: tensor -> out_dir/<name>.npy as float32 (exact for the fp32 / fp16 / bf16 tiers). Above DUMP_MAX_BYTES it is written
+    as a sample of its rows (last dimension kept whole, rows drawn with DUMP_SAMPLE_SEED and kept in order), so the same shape always yields
+    the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = t.detach().float().cpu().numpy()
+    budget, note = DUMP_MAX_BYTES - 4096, ""              # room for the .npy header
+    if a.nbytes > budget:
+        rows = a.reshape(-1, a.shape[-1])
+        keep = max(1, budget // (rows.shape[1] * a.itemsize))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows.shape[0], keep, replace=False))
+        note = f" (seeded sample of {keep} of {rows.shape[0]} rows of {list(a.shape)})"
+        a = rows[idx]
+    path = os.path.join(out_dir, name + ".npy")
+    np.save(path, np.ascontiguousarray(a))
+    print(f"dump-outputs: {name} {list(a.shape)} float32{note} -> {path}", file=sys.stderr, flush=True)
 
 
 DENOISER_TFLOP = {"s512": 0.804, "s1024": 9 * 0.804, "f1024": 74.4}      # per image (SURVEY 8(d): 0.804 per 64 x 64 UNet tile, 74.4 per Flux forward)

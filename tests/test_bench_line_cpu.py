@@ -4,6 +4,8 @@ import importlib.util
 import json
 import os
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -63,3 +65,33 @@ def test_compact_line_survives_failed_legs_and_oversize():
     full["other_tiers"] = {f"tier{i}": {"ms_per_step": 1.0, "images_per_s": 1.0, "rel_l2": 1e-4} for i in range(200)}
     line = b.compact_line(full, "S", 1024, 4, True, "fp32", "bench_detail.json", {})
     assert len(json.dumps(line)) <= b.MAX_LINE_BYTES and "roofline" in line and "cpu_baseline" in line
+
+
+def test_steps_and_dump_outputs_arguments():
+    b = _bench()
+    a = b.parse(["--steps", "7", "--warmup", "0", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "out"
+    assert b.parse([]).dump_outputs == ""
+    for argv in (["--steps", "0"], ["--warmup", "-1"], ["--dump-outputs", "out", "--dry-run-cpu"]):
+        with pytest.raises(SystemExit):
+            b.parse(argv)
+
+
+def test_dump_outputs_is_exact_float32_and_a_fixed_sample_above_the_budget(tmp_path):
+    """--dump-outputs: the step's output as float32 (bit-exact for every tier's dtype) when it fits the budget; above it, the same seeded
+    sample of whole rows on every call, within the budget."""
+    import numpy as np
+    import torch
+    b = _bench()
+    img = torch.randn(2, 3, 64, 48, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    b.dump_output(str(tmp_path / "a"), "image", img)
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.float().numpy())
+    b.DUMP_MAX_BYTES = 4096 + 2 * 3 * 64 * 48 * 4 // 3      # a third of the rows fit
+    for d in ("b", "c"):
+        b.dump_output(str(tmp_path / d), "image", img)
+    s1, s2 = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "c" / "image.npy")
+    assert np.array_equal(s1, s2) and s1.dtype == np.float32 and s1.shape[1] == 48 and 0 < s1.shape[0] < 2 * 3 * 64
+    assert os.path.getsize(tmp_path / "b" / "image.npy") <= b.DUMP_MAX_BYTES
+    rows = img.float().numpy().reshape(-1, 48)
+    assert all(any(np.array_equal(r, q) for q in rows) for r in s1)
