@@ -64,6 +64,13 @@ extern "C" {
  * and 7 zero bytes. a_lo' = a - a_hi, a_hi' = a_hi; scale = max(0, biased exponent of the block's largest magnitude - 2), codes round to
  * nearest even and saturate at +-7.5. The f8f6f4 MFMA runs such chunks in 8 passes where fp8 takes 16. */
 #define OMGSR_EL_MX6 4
+/* OMGSR_EL_MXFP8 (ABI v18; the fp8 tier's token-GEMM operand and weight form, OCP MX v1.0 MXFP8): a CODE plane and a SCALE plane.
+ *   codes  uint8 [rows][K], row stride K: OCP e4m3fn (not fnuz), one per element
+ *   scales uint8 [rows][K / 32], row stride K / 32: one E8M0 exponent per 32 consecutive K elements of a row
+ * scale = max(0, biased exponent of the block's largest |v| - 8); code = v 2^(127 - scale) rounded to nearest even and saturated at
+ * +-448, i.e. (v / 2^(scale - 127)).clamp(-448, 448).to(float8_e4m3fn); an all-zero block has scale 0 and zero codes. K % 128 == 0.
+ * Written by omgsr_quantize_mxfp8 (activations per call, weights at pack time); read by omgsr_igemm with `mxf8` = 1. */
+#define OMGSR_EL_MXFP8 5
 
 #define OMGSR_DT_BF16 0
 #define OMGSR_DT_F16 1
@@ -170,6 +177,16 @@ typedef struct omgsr_igemm_args {
     int32_t mx_fmt;        /* mx_chunks16 > 0: format of the correction chunks - 0 (or 8): OMGSR_EL_MX (fp8 e4m3, per-tensor scales mx_scale_*);
                               6: OMGSR_EL_MX6 (fp6 e2m3 with one E8M0 scale byte per 32-channel block, in the data; 3x3 convs of the halo-tile
                               kernel only, nine-tap and phase forms). Operand and weight carry the same format. */
+    /* ---- ABI v18: MXFP8 x MXFP8 (the fp8 tier's DiT token linears) */
+    int32_t mxf8;          /* 1: `in` and `weight` are OMGSR_EL_MXFP8 code planes (in: [batch][M][Cin] bytes, weight: [Cout_pad][K_pad] bytes,
+                              K_pad == Cin) with their scale planes below; the strides in_bstride / w_bstride count BYTES, the scale planes'
+                              batch strides are those divided by 32. GEMM-shaped problems only (1x1, stride 1, no padding / upsampling),
+                              Cin % 128 == 0, Cout_pad % 256 == 0, in_ld 0, bf16 compute type, none of the split / MX / GroupNorm fields:
+                              anything else returns OMGSR_E_SHAPE (never another kernel). Every output form of the 16-bit epilogue (bias, act,
+                              gate, residual, out_ld, LAYOUT_T, grid.z) applies. No split-K: a row's result does not depend on the batch */
+    int32_t mxf8_reserved; /* 0 */
+    const uint8_t* in_scale;    /* E8M0 [batch][M][Cin / 32] */
+    const uint8_t* w_scale;     /* E8M0 [Cout_pad][K_pad / 32] (w_bstride / 32 per grid.z entry) */
 } omgsr_igemm_args;
 /* 1 when omgsr_igemm / omgsr_igemm_multi would run these arguments with the GroupNorm apply fused into the conv's patch producer (the
  * fields above may still be unset: the answer depends on geometry, operand / weight form, compute type and `in_el` only; for a problem of a
@@ -262,6 +279,10 @@ int omgsr_groupnorm_apply_shared(const void* x, void* y, const float* mean, cons
  */
 int omgsr_layernorm(const void* x, void* y, const float* a, const float* b, int64_t rows, int32_t C,
                     float eps, int32_t x_el, int32_t y_el, void* stream);
+/* ABI v18: x (bf16 or f32 per x_el: OMGSR_EL_16 with the bf16 compute type, or OMGSR_EL_F32) [rows][x_ld] -> the OMGSR_EL_MXFP8 form of
+ * its first K columns: codes [rows][K], scales [rows][K / 32]. K % 128 == 0, x_ld >= K, x_ld % 8 == 0. Activations of the fp8 tier (one
+ * pass per LayerNorm output / attention output / FF hidden, shared by every consumer) and weights at pack time. */
+int omgsr_quantize_mxfp8(const void* x, int32_t x_el, int64_t rows, int32_t K, int64_t x_ld, void* codes, void* scales, void* stream);
 /* Stream tensor -> MFMA operand: y = x rounded to the compute type (y_el OMGSR_EL_16) or its two-term split
  * (OMGSR_EL_SPLIT); x f32 [rows][C], C % 8 == 0. (Inputs of convs that no norm precedes: up / down-sampling convs,
  * 1x1 shortcuts, conv_in, proj_out, post_quant_conv.) */
@@ -421,7 +442,7 @@ int omgsr_timing_reset(void);
 /* kind: 1 igemm, 2 attention, 3 groupnorm, 4 layernorm, 5 elementwise, 6 softmax. variant (igemm only): which kernel
  * the dispatcher launched - 1 igemm_kernel (register staged), 2 igemm_dma_kernel, 3 igemm_halo_kernel, 4 igemm_dma_kernel
  * split-K + splitk_reduce_kernel, 5 igemm_p8_kernel, 6 igemm_halo_kernel in its phase-decomposed upsampling form, 7 / 8
- * igemm_halo_multi_kernel (several problems of one layer in one launch: nine-tap / phase-decomposed form). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
+ * igemm_halo_multi_kernel (several problems of one layer in one launch: nine-tap / phase-decomposed form), 18 mxfp8_gemm_kernel (ABI v18). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;
 int omgsr_timing_collect(omgsr_timing_entry* out, int cap);

@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 from .build import lib_path
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class OmgsrError(RuntimeError):
@@ -40,6 +40,7 @@ class IgemmArgs(C.Structure):
         ("in_ld", C.c_int32), ("w_split", C.c_int32), ("weight_ph", C.c_void_p), ("mx_chunks16", C.c_int32), ("mx_scale_w1", C.c_int32), ("mx_scale_a1", C.c_int32),
         ("mx_scale_w2", C.c_int32), ("mx_scale_a2", C.c_int32), ("out_mx", C.c_int32), ("group_tiles", C.c_int32), ("overflow_flag", C.c_void_p),
         ("gn_scale_shift", C.c_void_p), ("gn_nimg", C.c_int32), ("gn_act", C.c_int32), ("in_el", C.c_int32), ("mx_fmt", C.c_int32),
+        ("mxf8", C.c_int32), ("mxf8_reserved", C.c_int32), ("in_scale", C.c_void_p), ("w_scale", C.c_void_p),
     ]
 
 
@@ -102,6 +103,7 @@ SIGNATURES = {
     "omgsr_resize_nearest_exact_nhwc": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
     "omgsr_transpose_split": (C.c_int, [_P, _P, _I, _I, _I, _L, _P]),
     "omgsr_to_operand": (C.c_int, [_P, _P, _L, _I, _I, _P, _P]),
+    "omgsr_quantize_mxfp8": (C.c_int, [_P, _I, _L, _I, _L, _P, _P, _P]),
     "omgsr_attention": (C.c_int, [C.POINTER(AttnArgs), _P]),
     "omgsr_softmax_rows": (C.c_int, [_P, _P, _L, _I, _I, _P]),
     "omgsr_softmax_rows_split": (C.c_int, [_P, _P, _L, _I, _I, _P]),

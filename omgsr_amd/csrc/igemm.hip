@@ -33,6 +33,8 @@ bool igemm_p8_wanted(const omgsr_igemm_args& a, const IgemmGeo& g);
 int igemm_p8_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
 bool igemm_gmx_ok(const omgsr_igemm_args& a);
 int igemm_gmx_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
+bool mxfp8_gemm_ok(const omgsr_igemm_args& a);                                 // gemm_mxfp8.hip: OMGSR_EL_MXFP8 operand and weight
+int mxfp8_gemm_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
 int igemm_halo_tiles(const omgsr_igemm_args& a, bool phase = false);
 bool igemm_halo_out6_ok(const omgsr_igemm_args& a);   // igemm_halo_out6.hip: the instantiations whose epilogue writes OMGSR_EL_MX6 can run this problem
 int igemm_halo_flat(const omgsr_igemm_args& a);      // pitch of the FLAT form the halo kernel would use for this problem (narrow maps), 0 = spatial tiles
@@ -509,7 +511,7 @@ extern "C" int32_t omgsr_igemm_gn_entries(const omgsr_igemm_args* ap) {
 }
 
 extern "C" int64_t omgsr_igemm_workspace_bytes(const omgsr_igemm_args* ap) {
-    if (!ap) return 0;
+    if (!ap || ap->mxf8) return 0;
     const int64_t M64 = (int64_t)ap->N * ap->Ho * ap->Wo;
     const int splits = splitk_plan(*ap, M64);
     if (splits < 2) return 0;
@@ -553,6 +555,9 @@ int validate_args(omgsr_igemm_args& a) {
     if (a.out_mx && (a.out_dtype != OMGSR_OUT_BF16 || a.out_layout != OMGSR_LAYOUT_NHWC || (a.Cout & 63) || a.out_lo_off || a.out_ld || a.gn_partial ||
                      omgsr::compute_dtype() != 1)) return OMGSR_E_SHAPE;
     if (a.gn_scale_shift && (a.gn_nimg <= 0 || a.gn_act != OMGSR_ACT_SILU || !gn_fusable(a))) return OMGSR_E_SHAPE;      // (SiLU is the one activation the producer applies)
+    // MXFP8 operand and weight (ABI v18): mxfp8_gemm_kernel or nothing
+    if (a.mxf8 != 0 && a.mxf8 != 1) return OMGSR_E_BADARG;
+    if (a.mxf8 && !omgsr::mxfp8_gemm_ok(a)) return OMGSR_E_SHAPE;
     if (a.gn_partial) {                            // must be exactly what omgsr_igemm_gn_slots / _gn_entries promised
         int nslot, entries;
         gn_plan(a, &nslot, &entries);
@@ -568,7 +573,8 @@ void work_of(const omgsr_igemm_args& a, double* flops, double* bytes) {
     // algorithmic work: a split operand's / weight's extra K segments are precision overhead, not useful FLOPs
     *flops = 2.0 * (double)M64 * (double)a.R * a.S * (a.Cin / ksegs) * (double)logical_cols * a.batch;
     const double out_b = (a.out_dtype == OMGSR_OUT_F32 ? 4.0 : (a.out_lo_off ? 4.0 : 2.0)), res_b = a.residual ? (a.res_el == OMGSR_EL_F32 ? 4.0 : 2.0) : 0.0;
-    *bytes = (2.0 * ((double)a.N * a.H * a.W * (a.in_ld > 0 ? a.in_ld : a.Cin) + (double)a.Cout_pad * a.K_pad) + (double)M64 * a.Cout * (out_b + res_b)) * a.batch;
+    const double eb = a.mxf8 ? 1.0 + 1.0 / 32.0 : 2.0;        // fp8 codes + their E8M0 scales
+    *bytes = (eb * ((double)a.N * a.H * a.W * (a.in_ld > 0 ? a.in_ld : a.Cin) + (double)a.Cout_pad * a.K_pad) + (double)M64 * a.Cout * (out_b + res_b)) * a.batch;
 }
 
 Geo geo_of(const omgsr_igemm_args& a) {
@@ -683,6 +689,10 @@ extern "C" int omgsr_igemm(const omgsr_igemm_args* ap, void* stream) {
     const omgsr_igemm_args pv = policy_view(a);
     const int64_t Mp = omgsr::g_batch_invariant ? (int64_t)pv.N * pv.Ho * pv.Wo : M64;
     const int64_t pbatch = omgsr::g_batch_invariant ? 1 : a.batch;
+    if (a.mxf8) {                                  // (validate_args: mxfp8_gemm_ok) no split-K, no other family: a row's bits do not depend on the batch
+        ts.rec.variant = 18;
+        return omgsr::mxfp8_gemm_launch(a, g, st);
+    }
     const int64_t tiles128 = ((Mp + 127) / 128) * (a.Cout_pad / 128) * pbatch;
     // Large problems: LDS-DMA kernel (256x128 tile, 3-stage ring). OMGSR_IGEMM_MODE=reg|dma overrides (A/B runs).
     static const char* mode = getenv("OMGSR_IGEMM_MODE");

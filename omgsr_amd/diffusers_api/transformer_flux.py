@@ -63,6 +63,11 @@ class FluxAttention(nn.Module, _Cached):
 
     def qk_packed(self, ctx: bool = False) -> ops.PackedWeight:
         q, k = (self.add_q_proj, self.add_k_proj) if ctx else (self.to_q, self.to_k)
+        if q.fp8 != k.fp8:
+            raise ValueError("the fused q|k projection needs to_q and to_k in one form (precision.set_fp8_linear moves them together)")
+        if q.fp8:
+            return self._cache("qk_ctx" if ctx else "qk", lambda: ops.pack_linear_weight_mxfp8(
+                torch.cat([q.weight, k.weight], 0), torch.cat([q.bias, k.bias], 0)), q.weight, k.weight, q.bias, k.bias, "fp8")
         sp, wsp = q.in_split(), q.in_wsplit()
         return self._cache("qk_ctx" if ctx else "qk", lambda: ops.pack_linear_weight(
             torch.cat([q.weight, k.weight], 0), torch.cat([q.bias, k.bias], 0), split=sp, w_split=wsp), q.weight, k.weight, q.bias, k.bias, sp, wsp)
@@ -71,6 +76,13 @@ class FluxAttention(nn.Module, _Cached):
         nq, nk = (self.norm_added_q, self.norm_added_k) if ctx else (self.norm_q, self.norm_k)
         return self._cache("nt_ctx" if ctx else "nt", lambda: torch.cat(
             [nq.w32()[None].expand(self.heads, -1), nk.w32()[None].expand(self.heads, -1)], 0).contiguous(), nq.weight, nk.weight)
+
+
+def _fp8_in(x: torch.Tensor, *layers):
+    """The operand each of `layers` reads from one producer's output x: the fp8 layers share ONE quantisation of x (ops.quantize_mxfp8),
+    the others read x itself."""
+    xq = ops.quantize_mxfp8(x) if any(l.fp8 for l in layers) else None
+    return [xq if l.fp8 else x for l in layers]
 
 
 class GELUProj(nn.Module):
@@ -131,15 +143,18 @@ class FluxTransformerBlock(nn.Module):
         cn = ops.layer_norm(c, mc["a1"], mc["b1"], 1e-6, split=at.add_q_proj.in_split())
         osp = at.to_out[0].in_split()                      # to_out and to_add_out read one buffer: same form (precision.check_policy)
         qk, vt, o = ws["qk"], ws["vt"], ws["o2" if osp == 2 else "o"]
-        ops.linear_into(cn, at.qk_packed(ctx=True), qk, 0, 0)
-        ops.linear_into(hn, at.qk_packed(), qk, Lc, 0)
-        ops.linear_t_into(cn, at.add_v_proj.packed(), vt, 0)
-        ops.linear_t_into(hn, at.to_v.packed(), vt, Lc)
+        cn_qk, cn_v = _fp8_in(cn, at.add_q_proj, at.add_v_proj)      # (fp8 tier: each LayerNorm output is quantised once)
+        hn_qk, hn_v = _fp8_in(hn, at.to_q, at.to_v)
+        ops.linear_into(cn_qk, at.qk_packed(ctx=True), qk, 0, 0)
+        ops.linear_into(hn_qk, at.qk_packed(), qk, Lc, 0)
+        ops.linear_t_into(cn_v, at.add_v_proj.packed(), vt, 0)
+        ops.linear_t_into(hn_v, at.to_v.packed(), vt, Lc)
         cos, sin = rope
         ops.rmsnorm_rope_(qk, at.norm_table(ctx=True), cos, sin, 2 * at.heads, at.head_dim, pos0=0, w_after=at.norm_table(), split_at=Lc)
         ops.attention(qk, qk, vt, at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=Lc + Li, out=o, out_split=osp)
-        h = ops.linear_rows(o, Lc, Li, at.to_out[0].packed(), residual=h, gate=mi["g1"])
-        c = ops.linear_rows(o, 0, Lc, at.to_add_out.packed(), residual=c, gate=mc["g1"])
+        o_out, o_add = _fp8_in(o, at.to_out[0], at.to_add_out)
+        h = ops.linear_rows(o_out, Lc, Li, at.to_out[0].packed(), residual=h, gate=mi["g1"])
+        c = ops.linear_rows(o_add, 0, Lc, at.to_add_out.packed(), residual=c, gate=mc["g1"])
         h = self.ff.run(ops.layer_norm(h, mi["a2"], mi["b2"], 1e-6, split=self.ff.net[0].proj.in_split()), h, mi["g2"])
         c = self.ff_context.run(ops.layer_norm(c, mc["a2"], mc["b2"], 1e-6, split=self.ff_context.net[0].proj.in_split()), c, mc["g2"])
         return h, c
@@ -168,13 +183,14 @@ class FluxSingleTransformerBlock(nn.Module):
         csp = self.proj_out.in_split()
         qk, vt, cat = ws["qk"], ws["vt"], ws["cat2" if csp == 2 else "cat"]
         Kc = D + self.mlp_hidden                           # the [attn | mlp] operand of proj_out; split form: [hi (Kc) | lo (Kc)]
-        ops.linear_into(xn.reshape(B * L, -1), at.qk_packed(), qk.reshape(B * L, -1), 0, 0, sample_rows=L)
-        ops.linear_t_into(xn, at.to_v.packed(), vt, 0)
+        xn_qk, xn_v, xn_mlp = _fp8_in(xn, at.to_q, at.to_v, self.proj_mlp)
+        ops.linear_into(xn_qk.reshape(B * L, -1), at.qk_packed(), qk.reshape(B * L, -1), 0, 0, sample_rows=L)
+        ops.linear_t_into(xn_v, at.to_v.packed(), vt, 0)
         ops.rmsnorm_rope_(qk, at.norm_table(), rope[0], rope[1], 2 * at.heads, at.head_dim, pos0=0)
         ops.attention(qk, qk, vt, at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=L, out=cat,
                       out_split=csp, o_lo_col=Kc)
         cat2d = cat.reshape(B * L, -1)
-        ops.linear_into(xn.reshape(B * L, -1), self.proj_mlp.packed(), cat2d, 0, D, act=ops.ACT_GELU_TANH, out_split=csp, lo_col0=Kc + D, sample_rows=L)
+        ops.linear_into(xn_mlp.reshape(B * L, -1), self.proj_mlp.packed(), cat2d, 0, D, act=ops.ACT_GELU_TANH, out_split=csp, lo_col0=Kc + D, sample_rows=L)
         return self.proj_out.nhwc(cat, residual=x, gate=mod["g"])
 
 

@@ -173,7 +173,13 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
 
 
 class Linear(nn.Linear, _Packed, _Operand):
+    # the fp8 tier (precision.set_fp8_linear): this layer runs as an MXFP8 x MXFP8 GEMM. The module keeps its bf16 weight (LoRA merges and
+    # in-place edits work as before); the packed form is quantised from it and joins the pack key, so an edit re-packs
+    fp8 = False
+
     def packed(self) -> ops.PackedWeight:
+        if self.fp8:
+            return self._packed(lambda: ops.pack_linear_weight_mxfp8(self.weight, self.bias), self.weight, self.bias, "fp8")
         sp, wsp = self.in_split(), self.in_wsplit()
         return self._packed(lambda: ops.pack_linear_weight(self.weight, self.bias, split=sp, w_split=wsp), self.weight, self.bias, sp, wsp)
 

@@ -27,7 +27,7 @@ from ._lib import AttnArgs, IgemmArgs, check
 ACT_NONE, ACT_SILU, ACT_GELU_TANH, ACT_GEGLU = 0, 1, 2, 3
 OUT_STREAM, OUT_BF16, OUT_F32 = -1, 0, 1      # conv / linear outputs: stream tensor (default) | 16-bit operand | fp32
 LAYOUT_NHWC, LAYOUT_T = 0, 1
-EL_16, EL_F32, EL_SPLIT, EL_MX, EL_MX6 = 0, 1, 2, 3, 4
+EL_16, EL_F32, EL_SPLIT, EL_MX, EL_MX6, EL_MXFP8 = 0, 1, 2, 3, 4, 5
 MX_LO_SHIFT = 11          # OMGSR_MX_LO_SHIFT (csrc/common.hip.h): a_lo' = (a - a_hi) * 2^11 as fp8
 
 
@@ -271,6 +271,12 @@ class PackedWeight:
     in_ld: int = 0     # physical channels of the operand row this weight expects (split * padded Cin); 0 = cin
     w_ph: Optional[torch.Tensor] = None   # 3x3 convs applied to a nearest-2x upsampled map: the four phase-summed 2 x 2 kernels,
                                           # [4][Kc/32][4 taps][Cout_pad][32] (omgsr_igemm_args.weight_ph): 4 / 9 of the MFMA work
+    w_scale: Optional[torch.Tensor] = None  # the fp8 tier's form (OMGSR_EL_MXFP8, pack_linear_weight_mxfp8): `w` holds the e4m3 codes
+                                            # uint8 [Cout_pad][K], this the E8M0 scales uint8 [Cout_pad][K / 32]
+
+    @property
+    def fp8(self) -> bool:
+        return self.w_scale is not None
 
     @property
     def cout_pad(self) -> int:
@@ -486,6 +492,77 @@ def pack_geglu_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], device
     pw.cout = inner
     pw.geglu = True
     return pw
+
+
+# --------------------------------------------------------------------------------------------
+# MXFP8 (the fp8 tier: include/omgsr_hip.h OMGSR_EL_MXFP8)
+
+@dataclass
+class Mxfp8:
+    """An OMGSR_EL_MXFP8 operand: e4m3fn codes uint8 [..., K] and E8M0 scales uint8 [..., K / 32] (one per 32 consecutive K values)."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+    def reshape(self, *lead) -> "Mxfp8":
+        """Reshape the leading dims (the K / K-block dim stays last)."""
+        lead = lead[:-1] if lead and lead[-1] == -1 else lead
+        return Mxfp8(self.codes.reshape(*lead, self.codes.shape[-1]), self.scales.reshape(*lead, self.scales.shape[-1]))
+
+
+def quantize_mxfp8(x: torch.Tensor) -> Mxfp8:
+    """x bf16 or fp32 [..., K] (K % 128 == 0) -> its OMGSR_EL_MXFP8 form, on the device (omgsr_quantize_mxfp8): scale = max(0, biased
+    exponent of the block's largest |v| - 8), code = (v / 2^(scale - 127)).clamp(-448, 448) in e4m3fn, round to nearest even."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"quantize_mxfp8: expected bfloat16 or float32, got {x.dtype}")
+    _req(x, x.dtype, "x")
+    K = x.shape[-1]
+    if K % 128:
+        raise ValueError(f"quantize_mxfp8: K = {K} is not a multiple of 128")
+    rows = x.numel() // K
+    codes = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+    scales = torch.empty((*x.shape[:-1], K // 32), device=x.device, dtype=torch.uint8)
+    check(_lib.load().omgsr_quantize_mxfp8(x.data_ptr(), EL_F32 if x.dtype == torch.float32 else EL_16, rows, K, K, codes.data_ptr(),
+                                           scales.data_ptr(), _stream()), "omgsr_quantize_mxfp8")
+    return Mxfp8(codes, scales)
+
+
+def pack_linear_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> PackedWeight:
+    """[out, in] bf16 -> the fp8 tier's weight: rows padded with zeros to a multiple of 256 and quantised on the device (quantize_mxfp8)."""
+    if _PRECISE or _ACT != torch.bfloat16:
+        raise ValueError("an fp8 (MXFP8) layer needs the bf16 compute type (the fp8 tier); the accurate tier and fp16 have none")
+    dev = device or weight.device
+    cout, cin = weight.shape
+    if cin % 128:
+        raise ValueError(f"an fp8 (MXFP8) layer needs in_features % 128 == 0, got {cin}")
+    w = torch.zeros((_round_up(cout, 256), cin), device=dev, dtype=torch.bfloat16)
+    w[:cout] = weight.detach().to(device=dev, dtype=torch.bfloat16)
+    q = quantize_mxfp8(w)
+    b = None if bias is None else bias.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return PackedWeight(q.codes, b, cout, cin, 1, 1, w_scale=q.scales)
+
+
+def _fp8_operand(x, pw: PackedWeight, what: str) -> Optional[Mxfp8]:
+    """The MXFP8 operand of an fp8 weight (a bf16 tensor is quantised here); None for the other weight forms, which take no MXFP8 operand."""
+    if not pw.fp8:
+        if isinstance(x, Mxfp8):
+            raise ValueError(f"{what}: an MXFP8 operand needs an fp8-packed weight")
+        return None
+    xq = x if isinstance(x, Mxfp8) else quantize_mxfp8(x)
+    if xq.codes.shape[-1] != pw.cin:
+        raise ValueError(f"{what}: operand K {xq.codes.shape[-1]} != weight K {pw.cin}")
+    return xq
+
+
+def _fill_mxfp8(a: IgemmArgs, codes_ptr: int, scales_ptr: int, pw: PackedWeight) -> None:
+    a.in_, a.in_scale = codes_ptr, scales_ptr
+    a.weight, a.w_scale, a.bias = pw.w.data_ptr(), pw.w_scale.data_ptr(), _ptr(pw.bias)
+    a.mxf8 = 1
+    a.Cin, a.Cout, a.Cout_pad, a.K_pad = pw.cin, pw.cout, pw.cout_pad, pw.k_pad
+    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
 
 
 # --------------------------------------------------------------------------------------------
@@ -728,7 +805,26 @@ def linear(x: torch.Tensor, pw: PackedWeight, *, act: int = ACT_NONE, residual: 
            gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM, alpha: float = 1.0, gn_groups: int = 0,
            out_split: int = 1) -> torch.Tensor:
     """x [..., K] -> [..., Cout]. gn_groups > 0 (x [B, ..., K]): the result feeds a GroupNorm over each x[b]; the GEMM
-    then runs as B images of prod(...) rows so its epilogue can leave the per-image statistics (see conv2d)."""
+    then runs as B images of prod(...) rows so its epilogue can leave the per-image statistics (see conv2d).
+    An fp8-packed weight (pack_linear_weight_mxfp8) takes an Mxfp8 operand, or quantises a bf16 `x` first."""
+    xq = _fp8_operand(x, pw, "linear")
+    if xq is not None:
+        if gn_groups or out_split != 1:
+            raise ValueError("linear: an fp8 layer writes a plain output (no GroupNorm statistics, no split)")
+        lead = xq.codes.shape[:-1]
+        M = xq.codes.numel() // pw.cin
+        out = _out_tensor(lead, pw.cout, out_dtype, 1, xq.codes.device)
+        if residual is not None and residual.numel() != M * pw.cout:
+            raise ValueError("linear: residual must be [..., Cout]")
+        a = IgemmArgs()
+        _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)
+        a.gate = _ptr(gate)
+        _fill_out(a, out, 1, residual, pw.cout)
+        a.N, a.H, a.W, a.Ho, a.Wo = 1, 1, M, 1, M
+        a.act, a.out_layout, a.batch, a.alpha = act, LAYOUT_NHWC, 1, alpha
+        a.sample_rows = M
+        check(_lib.load().omgsr_igemm(C.byref(a), _stream()), "omgsr_igemm(linear, mxfp8)")
+        return out
     lead = x.shape[:-1]
     M = 1
     for d in lead:
@@ -756,10 +852,18 @@ def linear_into(x: torch.Tensor, pw: PackedWeight, out: torch.Tensor, row0: int,
                 lo_col0: Optional[int] = None, sample_rows: int = 0) -> None:
     """out[row0:row0+M, col0:col0+Cout] = epilogue(x @ W^T): writes a projection straight into a slice of a
     larger 2-D operand buffer `out` [rows, ld] (joint text+image sequences, [attn | mlp] concat). out_split 2: the low
-    halves of the two-term split go to columns lo_col0 ... lo_col0+Cout of the same rows (default col0 + Cout)."""
-    if x.dtype == torch.float32:
+    halves of the two-term split go to columns lo_col0 ... lo_col0+Cout of the same rows (default col0 + Cout).
+    An fp8-packed weight takes an Mxfp8 operand (or quantises `x`)."""
+    xq = _fp8_operand(x, pw, "linear_into")
+    if xq is not None:
+        if out_split != 1:
+            raise ValueError("linear_into: an fp8 layer writes a plain output")
+        x = xq.codes
+    elif x.dtype == torch.float32:
         x = to_operand(x, pw.split)
-    _req(x, act_dtype(), "x"); _req(out, act_dtype(), "out")
+    if xq is None:
+        _req(x, act_dtype(), "x")
+    _req(out, act_dtype(), "out")
     # out [rows, ld], or [B, rows, ld] with x [B, M, K]: image b's M rows land at rows row0 .. row0+M of out[b] (grid.z = B)
     Bz = out.shape[0] if out.dim() == 3 else 1
     M, K = x.numel() // x.shape[-1] // Bz, x.shape[-1]
@@ -788,6 +892,8 @@ def linear_into(x: torch.Tensor, pw: PackedWeight, out: torch.Tensor, row0: int,
     a.batch, a.alpha = Bz, 1.0
     a.in_bstride, a.w_bstride, a.out_bstride = M * K, 0, nrows * ld
     a.sample_rows = sample_rows or M              # rows of ONE image when the caller flattened a batch into M (batch-invariant dispatch)
+    if xq is not None:
+        _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)
     _igemm(a, x.device, "omgsr_igemm(linear_into)", z_batched_api=True)
 
 
@@ -795,8 +901,12 @@ def linear_rows(x_buf: torch.Tensor, row0: int, rows: int, pw: PackedWeight, *, 
                 gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM) -> torch.Tensor:
     """out[b] = epilogue(x_buf[b, row0:row0+rows] @ W^T) for an operand buffer x_buf [B, L, K]: a projection of a row range of
     every image's joint sequence (to_out / to_add_out after joint attention) without gathering the rows first. Returns a dense
-    [B, rows, Cout] stream tensor; residual: dense [B, rows, Cout]."""
-    _req(x_buf, act_dtype(), "x_buf")
+    [B, rows, Cout] stream tensor; residual: dense [B, rows, Cout]. An fp8-packed weight takes an Mxfp8 x_buf (or quantises it)."""
+    xq = _fp8_operand(x_buf, pw, "linear_rows")
+    if xq is not None:
+        x_buf = xq.codes
+    else:
+        _req(x_buf, act_dtype(), "x_buf")
     B, L, K = x_buf.shape
     if K != pw.row_channels or row0 < 0 or row0 + rows > L:
         raise ValueError("linear_rows: row range / channels do not fit")
@@ -815,16 +925,23 @@ def linear_rows(x_buf: torch.Tensor, row0: int, rows: int, pw: PackedWeight, *, 
     a.batch, a.alpha = B, 1.0
     a.in_bstride, a.w_bstride, a.out_bstride = L * K, 0, rows * pw.cout
     a.sample_rows = rows
+    if xq is not None:
+        _fill_mxfp8(a, x_buf.data_ptr() + row0 * K, xq.scales.data_ptr() + row0 * (K // 32), pw)
     check(_lib.load().omgsr_igemm(C.byref(a), _stream()), "omgsr_igemm(linear_rows)")
     return out
 
 
 def linear_t_into(x: torch.Tensor, pw: PackedWeight, out_t: torch.Tensor, key0: int) -> None:
     """out_t[n, key0 + l] = (x W^T + b)[l, n] for x [L, K]: transposed projection into a slice of a joint
-    V^T buffer [Cout, ld]."""
-    if x.dtype == torch.float32:
+    V^T buffer [Cout, ld]. An fp8-packed weight takes an Mxfp8 operand (or quantises `x`)."""
+    xq = _fp8_operand(x, pw, "linear_t_into")
+    if xq is not None:
+        x = xq.codes
+    elif x.dtype == torch.float32:
         x = to_operand(x, pw.split)
-    _req(x, act_dtype(), "x"); _req(out_t, act_dtype(), "out_t")
+    if xq is None:
+        _req(x, act_dtype(), "x")
+    _req(out_t, act_dtype(), "out_t")
     # out_t [Cout, ld], or [B, Cout, ld] with x [B, L, K] (grid.z = B)
     Bz = out_t.shape[0] if out_t.dim() == 3 else 1
     L, K = x.numel() // x.shape[-1] // Bz, x.shape[-1]
@@ -842,6 +959,8 @@ def linear_t_into(x: torch.Tensor, pw: PackedWeight, out_t: torch.Tensor, key0: 
     a.batch, a.alpha = Bz, 1.0
     a.in_bstride, a.w_bstride, a.out_bstride = L * K, 0, pw.cout * out_t.shape[-1]
     a.sample_rows = L
+    if xq is not None:
+        _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)
     check(_lib.load().omgsr_igemm(C.byref(a), _stream()), "omgsr_igemm(linear_t_into)")
 
 

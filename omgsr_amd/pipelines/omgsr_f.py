@@ -44,6 +44,14 @@ class OMGSR_F_Infer(torch.nn.Module):
                  mid_timestep: int = 244, guidance_scale: float = 1.0, vae: Optional[AutoencoderKL] = None,
                  flux_transformer: Optional[FluxTransformer2DModel] = None, verbose: bool = False, precision_policy=None):
         super().__init__()
+        # weight_dtype=torch.float8_e4m3fn: the fp8 tier - the bf16 tier with the DiT's token linears as MXFP8 x MXFP8 GEMMs (precision.FLUX_FP8;
+        # precision_policy={"flux": {"fp8": [patterns]}} narrows the list). Modules are held and LoRA-merged in bf16, their fp8 forms packed lazily.
+        fp8 = weight_dtype == torch.float8_e4m3fn
+        if fp8 and precision_policy is not None and not (isinstance(precision_policy, dict) and set(precision_policy) <= {"flux"} and
+                                                         set(precision_policy.get("flux", {})) <= {"fp8"}):
+            raise ValueError("the fp8 tier's precision_policy is {'flux': {'fp8': [patterns]}} (a narrowing of precision.FLUX_FP8)")
+        fp8_patterns = (precision_policy or {}).get("flux", {}).get("fp8") if fp8 else None
+        weight_dtype = torch.bfloat16 if fp8 else weight_dtype
         ops.set_compute_dtype(weight_dtype)       # --weight_dtype picks the tier (bf16 | fp16 fast, fp32 accurate: see OMGSR_S_Infer)
         if vae is None:
             vae = AutoencoderKL.from_pretrained(flux_path, subfolder="vae")
@@ -68,6 +76,12 @@ class OMGSR_F_Infer(torch.nn.Module):
         self.device = device
         self.verbose = verbose
         from ..precision import RangeFallback
+        self.fp8 = fp8
+        from ..precision import FLUX_FP8, clear_fp8_linear, set_fp8_linear
+        if fp8:
+            set_fp8_linear(self.flux_transformer, FLUX_FP8 if fp8_patterns is None else fp8_patterns)
+        else:
+            clear_fp8_linear(self.flux_transformer)
         if weight_dtype == torch.float32:
             from ..precision import resolve
             resolve(precision_policy, vae=self.vae, flux=self.flux_transformer)

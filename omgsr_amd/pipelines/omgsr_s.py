@@ -30,6 +30,8 @@ class OMGSR_S_Infer(torch.nn.Module):
         (infer/omgsr_s_infer_model.py:11-25); `vae=` / `unet=` inject already-built modules instead
         (synthetic-weight benchmarks and tests — there are no checkpoints on the GPU box)."""
         super().__init__()
+        if weight_dtype == torch.float8_e4m3fn:
+            raise ValueError("OMGSR-S has no fp8 tier (the fp8 tier is OMGSR-F's DiT token GEMMs): use bfloat16, float16 or float32")
         # --weight_dtype picks the tier: bf16 / fp16 = that 16-bit type end to end; fp32 = the accurate tier (fp32 stream
         # tensors, fp16 MFMA operands, two-term split operands where the precision policy says so)
         ops.set_compute_dtype(weight_dtype)

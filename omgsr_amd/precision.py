@@ -205,6 +205,58 @@ def set_mx_linear(model: nn.Module, patterns: Iterable[str]) -> int:
     return n
 
 
+# ---- the fp8 tier (OMGSR_F_Infer(weight_dtype=torch.float8_e4m3fn)): bf16 compute and stream type, MXFP8 x MXFP8 token GEMMs -------------------
+# The DiT's per-token linears: the fused q|k and V projections of both streams, to_out / to_add_out, both FF layers of both streams, proj_mlp /
+# proj_out of the single blocks. Everything else (attention, x_embedder, context_embedder, the final norm_out / proj_out, the folded AdaLN
+# constants, the VAE) stays bf16. FP8_ELIGIBLE is the hard limit: set_fp8_linear only ever marks modules it matches, so a user list narrows.
+FP8_ELIGIBLE = [r"^transformer_blocks\.\d+\.attn\.(to_q|to_k|to_v|add_q_proj|add_k_proj|add_v_proj|to_out\.0|to_add_out)$",
+                r"^transformer_blocks\.\d+\.(ff|ff_context)\.net\.(0\.proj|2)$",
+                r"^single_transformer_blocks\.\d+\.(proj_mlp|proj_out)$",
+                r"^single_transformer_blocks\.\d+\.attn\.(to_q|to_k|to_v)$"]
+FLUX_FP8 = list(FP8_ELIGIBLE)
+
+
+def set_fp8_linear(model: nn.Module, patterns: Iterable[str]) -> int:
+    """Mark the Linear layers of a FluxTransformer2DModel whose names match `patterns` (and FP8_ELIGIBLE) as fp8 (nn.Linear.fp8): they then
+    run as MXFP8 x MXFP8 GEMMs on their lazily quantised bf16 weights. The two halves of a fused q|k projection move together (both match or
+    neither moves). Every other Linear is unmarked. Needs the bf16 compute type: ValueError in the accurate tier and with fp16. Returns how
+    many layers are fp8."""
+    from . import ops
+    if ops.precise() or ops.act_dtype() != torch.bfloat16:
+        raise ValueError("fp8 layers need the bf16 compute type (the fp8 tier); the accurate tier and fp16 have none")
+    _touch()
+    regs = [re.compile(p) for p in patterns]
+    elig = [re.compile(p) for p in FP8_ELIGIBLE]
+    hit = lambda name: any(r.search(name) for r in regs) and any(r.search(name) for r in elig)      # noqa: E731
+    mods = dict(model.named_modules())
+    want = {name for name, m in mods.items() if isinstance(m, Linear) and hit(name)}
+    for name in list(want):                     # q | k pairs: both or neither
+        for a, b in (("to_q", "to_k"), ("add_q_proj", "add_k_proj")):
+            for x, y in ((a, b), (b, a)):
+                if name.endswith("." + x) and name[: -len(x)] + y not in want:
+                    want.discard(name)
+    n = 0
+    for name, m in mods.items():
+        if isinstance(m, Linear):
+            m.fp8 = name in want
+            n += m.fp8
+    return n                                    # (the pack keys carry the form: a moved layer re-packs at its next call)
+
+
+def clear_fp8_linear(model: nn.Module) -> None:
+    """Unmark every fp8 Linear of `model` (a pipeline of another tier built on modules an fp8-tier pipeline marked)."""
+    if any(isinstance(m, Linear) and m.fp8 for m in model.modules()):
+        _touch()
+        for m in model.modules():
+            if isinstance(m, Linear):
+                m.fp8 = False
+
+
+def fp8_layers(model: nn.Module) -> list:
+    """Names of the fp8 Linear layers of `model`."""
+    return [name for name, m in model.named_modules() if isinstance(m, Linear) and m.fp8]
+
+
 def set_mx(model: nn.Module, patterns: Iterable[str]) -> int:
     """Move the both-sides split of the matching 3x3 stride-1 (halo-tile kernel) and 1x1 (MX GEMM kernel) convolutions (Cin % 64 == 0,
     >= 96 output channels) to the mixed-precision form (op_split 3); layers that do not qualify keep what they had. OMGSR_MX=0

@@ -84,3 +84,25 @@ def psnr(got: torch.Tensor, ref: torch.Tensor, peak: float = 2.0) -> float:
     got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
     mse = (got - ref).pow(2).mean().item()
     return float("inf") if mse == 0 else 10.0 * math.log10(peak * peak / mse)
+
+
+def mxfp8_ref(x: torch.Tensor):
+    """Reference OMGSR_EL_MXFP8 quantiser (include/omgsr_hip.h) on the host: x [..., K] (K % 32 == 0) -> (codes uint8 [..., K],
+    scales uint8 [..., K / 32]). scale = max(0, biased exponent of the block's largest |v| - 8); code = (v / 2^(scale - 127)).clamp(-448, 448)
+    as e4m3fn (the clamp first: torch does not saturate on this cast). The division is done as the exact multiplication by 2^(127 - scale)."""
+    x = x.float()
+    K = x.shape[-1]
+    blk = x.reshape(*x.shape[:-1], K // 32, 32)
+    e = (blk.abs().amax(-1).view(torch.int32) >> 23) & 0xFF
+    s = (e - 8).clamp(min=0)
+    q = (blk * torch.exp2((127 - s).float())[..., None]).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)
+    return q.reshape(x.shape), s.to(torch.uint8)
+
+
+def mxfp8_dequant(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """The values an MXFP8 (codes, scales) pair stands for, in float64 (exact)."""
+    lut = torch.arange(256, dtype=torch.int32).to(torch.uint8).view(torch.float8_e4m3fn).double().to(codes.device)
+    v = lut[codes.long()]
+    K = v.shape[-1]
+    s = torch.exp2(scales.double() - 127)
+    return (v.reshape(*v.shape[:-1], K // 32, 32) * s[..., None]).reshape(v.shape)
