@@ -322,6 +322,20 @@ typedef struct omgsr_attn_args {
     int64_t vt_lo_off;     /* > 0 (with the q / k split): V^T is a two-term split too - the low halves of [H*D][vt_ld] start vt_lo_off ELEMENTS after
                               vt (omgsr_transpose_split writes [B][2 H D][ld]: vt_lo_off = H * D * vt_ld, vt_bstride = 2 H D vt_ld); O^T gains the
                               V_lo^T P_hi^T pass */
+    /* ---- ABI v19: MXFP8 joint attention (the fp8 tier's opt-in `fp8_attention`) */
+    int32_t qkv_el;        /* OMGSR_EL_16 (0: everything above) | OMGSR_EL_MXFP8: q, k and vt are OMGSR_EL_MXFP8 code planes (bytes: q_ld / k_ld /
+                              vt_ld and the batch strides count bytes) with the scale planes below - q, k one E8M0 per 32 consecutive head-dim
+                              values, vt one per 32 consecutive keys of a channel row - and mxfp8_attn_kernel runs softmax(Q K^T scale) V with
+                              v_mfma_scale_f32_32x32x64_f8f6f4. The probabilities enter the PV product as e4m3(P 2^8) with scale 2^-8 under an exact
+                              running maximum, and the row sum adds those dequantised values. o is bf16 as for OMGSR_EL_16. D = 128, vt_ld % 128 == 0,
+                              16-byte aligned code rows, 4-byte aligned scale rows, bf16 compute type, none of o_lo_off / o_mx / the split fields:
+                              anything else returns OMGSR_E_SHAPE. Keys >= Lk are masked (k rows and vt columns there are never used). */
+    int32_t qkv_reserved;  /* 0 */
+    const uint8_t* q_scale;     /* E8M0 [B][Lq][q_sld], head h at byte 4h */
+    const uint8_t* k_scale;     /* E8M0 [B][Lk][k_sld], head h at byte 4h */
+    const uint8_t* vt_scale;    /* E8M0 [B][H*D][vt_sld] (vt_sld >= vt_ld / 32) */
+    int64_t q_sld, k_sld, vt_sld;                 /* scale row strides (bytes) */
+    int64_t q_sbstride, k_sbstride, vt_sbstride;  /* scale batch strides (bytes; 0 broadcasts with kv_bstride 0) */
 } omgsr_attn_args;
 /* Process-wide (default 0): the online softmax moves its running maximum only when a row's maximum grows by more than 2^t in
  * the scaled base-2 domain (probabilities then reach 2^t instead of 1; the result is the same quotient). 0 = exact running
@@ -347,6 +361,13 @@ int omgsr_softmax_rows_split(const float* s, void* p, int64_t rows, int32_t L, i
 int omgsr_rmsnorm_rope(void* x, const float* w, const float* w2, int32_t Lsplit, const float* cos_t, const float* sin_t, int32_t B,
                        int32_t L, int32_t H, int32_t D, int64_t ld, int32_t col0, int32_t pos0,
                        float eps, void* stream);
+/* ABI v19: the same RMSNorm + RoPE with the fp32 result written in the OMGSR_EL_MXFP8 form (the q | k operand of the MXFP8 attention) instead
+ * of in place: x (bf16 compute type) is read only; codes uint8 [B*L][c_ld] get head h at byte col0 + h*D, scales uint8 [B*L][s_ld] at byte
+ * col0 / 32 + h*D / 32, by omgsr_quantize_mxfp8's rule applied to the fp32 values (a 32-value block lies inside one head). D = 128,
+ * col0 % 128 == 0, c_ld % 16 == 0, s_ld % 4 == 0. */
+int omgsr_rmsnorm_rope_mxfp8(const void* x, const float* w, const float* w2, int32_t Lsplit, const float* cos_t, const float* sin_t, int32_t B,
+                             int32_t L, int32_t H, int32_t D, int64_t ld, int32_t col0, int32_t pos0, float eps, void* codes, void* scales,
+                             int64_t c_ld, int64_t s_ld, void* stream);
 
 /* K14 — layout and latent algebra. */
 /* NCHW (f32 or bf16 per src_dtype: 0 bf16, 1 f32) -> NHWC bf16 with channels zero-padded to Cpad. */
@@ -442,7 +463,8 @@ int omgsr_timing_reset(void);
 /* kind: 1 igemm, 2 attention, 3 groupnorm, 4 layernorm, 5 elementwise, 6 softmax. variant (igemm only): which kernel
  * the dispatcher launched - 1 igemm_kernel (register staged), 2 igemm_dma_kernel, 3 igemm_halo_kernel, 4 igemm_dma_kernel
  * split-K + splitk_reduce_kernel, 5 igemm_p8_kernel, 6 igemm_halo_kernel in its phase-decomposed upsampling form, 7 / 8
- * igemm_halo_multi_kernel (several problems of one layer in one launch: nine-tap / phase-decomposed form), 18 mxfp8_gemm_kernel (ABI v18). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
+ * igemm_halo_multi_kernel (several problems of one layer in one launch: nine-tap / phase-decomposed form), 18 mxfp8_gemm_kernel (ABI v18).
+ * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;
 int omgsr_timing_collect(omgsr_timing_entry* out, int cap);

@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 from .build import lib_path
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 class OmgsrError(RuntimeError):
@@ -61,6 +61,10 @@ class AttnArgs(C.Structure):
         ("q_bstride", C.c_int64), ("k_bstride", C.c_int64), ("vt_bstride", C.c_int64), ("o_bstride", C.c_int64),
         ("scale", C.c_float), ("o_lo_off", C.c_int32), ("o_mx", C.c_int32), ("q_lo_off", C.c_int32), ("k_lo_off", C.c_int32), ("p_split", C.c_int32),
         ("reserved1", C.c_int32), ("vt_lo_off", C.c_int64),
+        # ABI v19: MXFP8 q / k / V^T (qkv_el = OMGSR_EL_MXFP8)
+        ("qkv_el", C.c_int32), ("qkv_reserved", C.c_int32), ("q_scale", C.c_void_p), ("k_scale", C.c_void_p), ("vt_scale", C.c_void_p),
+        ("q_sld", C.c_int64), ("k_sld", C.c_int64), ("vt_sld", C.c_int64), ("q_sbstride", C.c_int64), ("k_sbstride", C.c_int64),
+        ("vt_sbstride", C.c_int64),
     ]
 
 
@@ -108,6 +112,7 @@ SIGNATURES = {
     "omgsr_softmax_rows": (C.c_int, [_P, _P, _L, _I, _I, _P]),
     "omgsr_softmax_rows_split": (C.c_int, [_P, _P, _L, _I, _I, _P]),
     "omgsr_rmsnorm_rope": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _L, _I, _I, _F, _P]),
+    "omgsr_rmsnorm_rope_mxfp8": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _L, _I, _I, _F, _P, _P, _L, _L, _P]),
     "omgsr_nchw_to_nhwc": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "omgsr_nhwc_to_nchw": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
     "omgsr_copy_channels": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _I, _P]),

@@ -499,6 +499,8 @@ int launch_attn(const omgsr_attn_args& a, hipStream_t st) {
 
 }  // namespace
 
+namespace omgsr { int mxfp8_attention(const omgsr_attn_args& a, hipStream_t st); }
+
 extern "C" int omgsr_set_attention_defer_max(float log2_threshold) {
     if (!(log2_threshold >= 0.0f && log2_threshold <= 12.0f)) return OMGSR_E_BADARG;
     g_defer_max = log2_threshold;
@@ -509,6 +511,8 @@ extern "C" int omgsr_attention(const omgsr_attn_args* ap, void* stream) {
     if (!ap || !ap->q || !ap->k || !ap->vt || !ap->o) return OMGSR_E_BADARG;
     const omgsr_attn_args a = *ap;
     if (a.B <= 0 || a.H <= 0 || a.Lq <= 0 || a.Lk <= 0) return OMGSR_E_BADARG;
+    if (a.qkv_el == OMGSR_EL_MXFP8) return omgsr::mxfp8_attention(a, (hipStream_t)stream);      // ABI v19: attention_mxfp8.hip
+    if (a.qkv_el != OMGSR_EL_16) return OMGSR_E_BADARG;
     if ((a.q_ld & 7) || (a.k_ld & 7) || (a.vt_ld & 7) || (a.o_ld & 3) || a.vt_ld < a.Lk) return OMGSR_E_SHAPE;
     if (a.o_lo_off < 0 || (a.o_lo_off && ((a.o_lo_off & 3) || a.o_lo_off < a.H * a.D || a.o_ld < (int64_t)a.o_lo_off + a.H * a.D))) return OMGSR_E_SHAPE;
     // MX output: the whole row belongs to this call (heads at column 0, o_ld = 2 H D slots), fp16 compute type

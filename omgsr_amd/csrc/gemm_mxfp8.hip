@@ -16,6 +16,7 @@
 #include "../../include/omgsr_hip.h"
 #include "timing.hip.h"
 #include "igemm_epilogue.hip.h"
+#include "mxfp8.hip.h"
 #include <type_traits>
 
 namespace {
@@ -251,22 +252,6 @@ __global__ __launch_bounds__(512, 2) void mxfp8_gemm_kernel(const omgsr_igemm_ar
 }
 
 // ---- quantiser: one thread per 32-element block ----------------------------------------------------------------------------
-// fp32 -> OCP e4m3fn, round to nearest even, |a| <= 448 (the caller clamps): the conversion of c10::Float8_e4m3fn, bit for bit
-OMGSR_DEVINL unsigned e4m3_rne(const float v) {
-    const unsigned bits = __float_as_uint(v);
-    const unsigned sign = (bits >> 24) & 0x80u;
-    const float a = __uint_as_float(bits & 0x7fffffffu);
-    unsigned code;
-    if (a < 0.015625f) {                                // below 2^-6: subnormal codes m 2^-9 (m = 8 is the smallest normal, code 8)
-        code = (unsigned)__builtin_rintf(a * 512.0f);
-    } else {
-        unsigned b = __float_as_uint(a);
-        b += 0x7ffffu + ((b >> 20) & 1u);               // round the 23-bit mantissa to 3 bits, ties to even
-        code = (b >> 20) - ((127u - 7u) << 3);
-    }
-    return sign | code;
-}
-
 template <typename TI>
 __global__ __launch_bounds__(256) void mxfp8_quantize_kernel(const TI* __restrict__ x, const int64_t rows, const int K, const int64_t x_ld,
                                                              unsigned char* __restrict__ codes, unsigned char* __restrict__ scales) {
@@ -298,15 +283,13 @@ __global__ __launch_bounds__(256) void mxfp8_quantize_kernel(const TI* __restric
     float mx = 0.0f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) mx = fmaxf(mx, fabsf(v[i]));
-    const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu);
-    const int s = e > 8 ? e - 8 : 0;
-    const float mul = __uint_as_float((unsigned)(254 - s) << 23);      // 2^(127 - s): a normal float for every s in [0, 246]
+    const int s = mxfp8_scale(mx);
     unsigned out[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         unsigned w = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) w |= e4m3_rne(fminf(fmaxf(v[4 * i + k] * mul, -448.0f), 448.0f)) << (8 * k);
+        for (int k = 0; k < 4; ++k) w |= mxfp8_code(v[4 * i + k], s) << (8 * k);
         out[i] = w;
     }
     uint4* dst = reinterpret_cast<uint4*>(codes + r * K + 32 * b);

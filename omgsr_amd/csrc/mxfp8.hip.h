@@ -1,0 +1,32 @@
+// The OMGSR_EL_MXFP8 element rule (include/omgsr_hip.h), shared by the quantiser (gemm_mxfp8.hip) and the kernels that write the form
+// directly (norm.hip: rmsnorm_rope_mxfp8_kernel).
+#pragma once
+#include "common.hip.h"
+
+// fp32 -> OCP e4m3fn, round to nearest even, |a| <= 448 (the caller clamps): the conversion of c10::Float8_e4m3fn, bit for bit
+OMGSR_DEVINL unsigned e4m3_rne(const float v) {
+    const unsigned bits = __float_as_uint(v);
+    const unsigned sign = (bits >> 24) & 0x80u;
+    const float a = __uint_as_float(bits & 0x7fffffffu);
+    unsigned code;
+    if (a < 0.015625f) {                                // below 2^-6: subnormal codes m 2^-9 (m = 8 is the smallest normal, code 8)
+        code = (unsigned)__builtin_rintf(a * 512.0f);
+    } else {
+        unsigned b = __float_as_uint(a);
+        b += 0x7ffffu + ((b >> 20) & 1u);               // round the 23-bit mantissa to 3 bits, ties to even
+        code = (b >> 20) - ((127u - 7u) << 3);
+    }
+    return sign | code;
+}
+
+// E8M0 scale of a block whose largest magnitude is mx: max(0, biased exponent - 8)
+OMGSR_DEVINL int mxfp8_scale(const float mx) {
+    const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu);
+    return e > 8 ? e - 8 : 0;
+}
+
+// code of v under scale s: (v 2^(127 - s)).clamp(-448, 448) in e4m3fn
+OMGSR_DEVINL unsigned mxfp8_code(const float v, const int s) {
+    const float mul = __uint_as_float((unsigned)(254 - s) << 23);      // 2^(127 - s): a normal float for every s in [0, 246]
+    return e4m3_rne(fminf(fmaxf(v * mul, -448.0f), 448.0f));
+}

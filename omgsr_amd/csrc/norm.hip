@@ -4,6 +4,7 @@
 #include <type_traits>
 #include "../../include/omgsr_hip.h"
 #include "timing.hip.h"
+#include "mxfp8.hip.h"
 #include <stdlib.h>
 
 namespace {
@@ -528,6 +529,57 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(T* __restrict__ x, co
     *reinterpret_cast<u32x4_t*>(px) = pack8<T>(f);
 }
 
+// The same RMSNorm + RoPE (bf16 in) with the fp32 result written as OMGSR_EL_MXFP8 codes + scales (the MXFP8 attention's q | k operand,
+// ABI v19): a 32-value block is 4 lanes of the head's 16, so its maximum is two more exchanges; codes / scales by omgsr_quantize_mxfp8's rule.
+__global__ __launch_bounds__(256) void rmsnorm_rope_mxfp8_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w, const float* __restrict__ w2,
+                                                                  int Lsplit, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                                  int64_t rows, int L, int H, int D, int64_t ld, int col0, int pos0, float eps,
+                                                                  unsigned char* __restrict__ codes, unsigned char* __restrict__ scales, int64_t c_ld,
+                                                                  int64_t s_ld) {
+    const int64_t gid = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);   // (row, head) index
+    if (gid >= rows * H) return;
+    const int sub = threadIdx.x & 15;
+    const int64_t row = gid / H;
+    const int h = (int)(gid - row * H);
+    const bf16_t* px = x + row * ld + col0 + h * D + sub * 8;
+    float f[8];
+    unpack8<bf16_t>(*reinterpret_cast<const u32x4_t*>(px), f);
+    float q = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q += f[e] * f[e];
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float r = rsqrtf(q / (float)D + eps);
+    const float* wt = (w2 && (int)(row % L) >= Lsplit) ? w2 : w;
+    float wv[8];
+    load_affine8(wt, h * D + sub * 8, 1.0f, wv);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = f[e] * r * wv[e];
+    if (cos_t) {
+        const int pos = pos0 + (int)(row % L);
+        float cp[8], sp[8];
+        load_affine8(cos_t, (int)((int64_t)pos * D) + sub * 8, 1.0f, cp);
+        load_affine8(sin_t, (int)((int64_t)pos * D) + sub * 8, 0.0f, sp);
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+            const float a = f[e], b = f[e + 1];
+            f[e] = a * cp[e] - b * sp[e];
+            f[e + 1] = b * cp[e + 1] + a * sp[e + 1];
+        }
+    }
+    float mx = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(f[e]));
+    mx = fmaxf(mx, __shfl_xor(mx, 1));
+    mx = fmaxf(mx, __shfl_xor(mx, 2));
+    const int s = mxfp8_scale(mx);
+    u32x2_t out = {0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[e >> 2] |= mxfp8_code(f[e], s) << (8 * (e & 3));
+    *reinterpret_cast<u32x2_t*>(codes + row * c_ld + col0 + h * D + sub * 8) = out;
+    if ((sub & 3) == 0) scales[row * s_ld + col0 / 32 + h * (D / 32) + (sub >> 2)] = (unsigned char)s;
+}
+
 }  // namespace
 
 extern "C" int omgsr_groupnorm_scale_shift(const float* mean, const float* rstd, const float* gamma, const float* beta, float* out, int32_t nimg,
@@ -767,6 +819,22 @@ extern "C" int omgsr_softmax_rows_split(const float* s, void* p, int64_t rows, i
     if (nv <= 1) OMGSR_DISPATCH_T(hipLaunchKernelGGL((softmax_rows_kernel<T, 1, true>), dim3((unsigned)rows), dim3(256), 0, st, s, (T*)p, L, Lvalid));
     else if (nv <= 4) OMGSR_DISPATCH_T(hipLaunchKernelGGL((softmax_rows_kernel<T, 4, true>), dim3((unsigned)rows), dim3(256), 0, st, s, (T*)p, L, Lvalid));
     else OMGSR_DISPATCH_T(hipLaunchKernelGGL((softmax_rows_kernel<T, 16, true>), dim3((unsigned)rows), dim3(256), 0, st, s, (T*)p, L, Lvalid));
+    return (int)hipGetLastError();
+}
+
+extern "C" int omgsr_rmsnorm_rope_mxfp8(const void* x, const float* w, const float* w2, int32_t Lsplit, const float* cos_t, const float* sin_t, int32_t B,
+                                        int32_t L, int32_t H, int32_t D, int64_t ld, int32_t col0, int32_t pos0, float eps, void* codes, void* scales,
+                                        int64_t c_ld, int64_t s_ld, void* stream) {
+    if (!x || !w || !codes || !scales || B <= 0 || L <= 0 || H <= 0) return OMGSR_E_BADARG;
+    if (D != 128 || (ld & 7) || (col0 & 127) || (c_ld & 15) || (s_ld & 3) || c_ld < (int64_t)col0 + (int64_t)H * D || s_ld < ((int64_t)col0 + (int64_t)H * D) / 32 ||
+        ((cos_t == nullptr) != (sin_t == nullptr)) || omgsr::compute_dtype() != 0)
+        return OMGSR_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t rows = (int64_t)B * L;
+    const int64_t groups = rows * H;
+    omgsr::TimingScope ts(OMGSR_TK_ELT, 0.0, (2.0 + 1.0 + 1.0 / 32.0) * (double)groups * D, st);
+    hipLaunchKernelGGL(rmsnorm_rope_mxfp8_kernel, dim3((unsigned)((groups + 15) / 16)), dim3(256), 0, st, (const bf16_t*)x, w, w2, Lsplit, cos_t, sin_t,
+                       rows, L, H, D, ld, col0, pos0, eps, (unsigned char*)codes, (unsigned char*)scales, c_ld, s_ld);
     return (int)hipGetLastError();
 }
 

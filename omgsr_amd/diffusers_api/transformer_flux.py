@@ -60,6 +60,7 @@ class FluxAttention(nn.Module, _Cached):
             self.norm_added_q, self.norm_added_k = RMSNormWeight(head_dim, 1e-6), RMSNormWeight(head_dim, 1e-6)
             self.to_add_out = Linear(inner, dim)
         self.to_out = None if pre_only else nn.ModuleList([Linear(inner, dim), nn.Dropout(0.0)])
+        self.fp8 = False        # the fp8 tier's opt-in MXFP8 attention (precision.set_fp8_attention)
 
     def qk_packed(self, ctx: bool = False) -> ops.PackedWeight:
         q, k = (self.add_q_proj, self.add_k_proj) if ctx else (self.to_q, self.to_k)
@@ -150,8 +151,14 @@ class FluxTransformerBlock(nn.Module):
         ops.linear_t_into(cn_v, at.add_v_proj.packed(), vt, 0)
         ops.linear_t_into(hn_v, at.to_v.packed(), vt, Lc)
         cos, sin = rope
-        ops.rmsnorm_rope_(qk, at.norm_table(ctx=True), cos, sin, 2 * at.heads, at.head_dim, pos0=0, w_after=at.norm_table(), split_at=Lc)
-        ops.attention(qk, qk, vt, at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=Lc + Li, out=o, out_split=osp)
+        if at.fp8:              # MXFP8 q | k straight out of RMSNorm + RoPE, V^T quantised once along the key index
+            qk8 = ops.rmsnorm_rope_mxfp8(qk, at.norm_table(ctx=True), cos, sin, 2 * at.heads, at.head_dim, pos0=0, w_after=at.norm_table(),
+                                         split_at=Lc, out=ws["qk8"])
+            ops.attention(qk8, qk8, ops.quantize_mxfp8(vt, out=ws["vt8"]), at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner,
+                          Lk=Lc + Li, out=o)
+        else:
+            ops.rmsnorm_rope_(qk, at.norm_table(ctx=True), cos, sin, 2 * at.heads, at.head_dim, pos0=0, w_after=at.norm_table(), split_at=Lc)
+            ops.attention(qk, qk, vt, at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=Lc + Li, out=o, out_split=osp)
         o_out, o_add = _fp8_in(o, at.to_out[0], at.to_add_out)
         h = ops.linear_rows(o_out, Lc, Li, at.to_out[0].packed(), residual=h, gate=mi["g1"])
         c = ops.linear_rows(o_add, 0, Lc, at.to_add_out.packed(), residual=c, gate=mc["g1"])
@@ -186,9 +193,14 @@ class FluxSingleTransformerBlock(nn.Module):
         xn_qk, xn_v, xn_mlp = _fp8_in(xn, at.to_q, at.to_v, self.proj_mlp)
         ops.linear_into(xn_qk.reshape(B * L, -1), at.qk_packed(), qk.reshape(B * L, -1), 0, 0, sample_rows=L)
         ops.linear_t_into(xn_v, at.to_v.packed(), vt, 0)
-        ops.rmsnorm_rope_(qk, at.norm_table(), rope[0], rope[1], 2 * at.heads, at.head_dim, pos0=0)
-        ops.attention(qk, qk, vt, at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=L, out=cat,
-                      out_split=csp, o_lo_col=Kc)
+        if at.fp8:
+            qk8 = ops.rmsnorm_rope_mxfp8(qk, at.norm_table(), rope[0], rope[1], 2 * at.heads, at.head_dim, pos0=0, out=ws["qk8"])
+            ops.attention(qk8, qk8, ops.quantize_mxfp8(vt, out=ws["vt8"]), at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=L,
+                          out=cat)
+        else:
+            ops.rmsnorm_rope_(qk, at.norm_table(), rope[0], rope[1], 2 * at.heads, at.head_dim, pos0=0)
+            ops.attention(qk, qk, vt, at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=L, out=cat,
+                          out_split=csp, o_lo_col=Kc)
         cat2d = cat.reshape(B * L, -1)
         ops.linear_into(xn_mlp.reshape(B * L, -1), self.proj_mlp.packed(), cat2d, 0, D, act=ops.ACT_GELU_TANH, out_split=csp, lo_col0=Kc + D, sample_rows=L)
         return self.proj_out.nhwc(cat, residual=x, gate=mod["g"])
@@ -347,8 +359,10 @@ class FluxTransformer2DModel(ModelMixin, _Cached):
         dev = x_tok.device
         mlp = self.single_transformer_blocks[0].mlp_hidden if len(self.single_transformer_blocks) else 0
         ad = ops.act_dtype()
+        fp8_attn = any(b.attn.fp8 for b in list(self.transformer_blocks) + list(self.single_transformer_blocks))
+        ldv = ops._round_up(L, 128 if fp8_attn else 8)          # (the MXFP8 V^T: whole 128-key rows for the quantiser)
         ws = dict(qk=torch.empty((B, L, 2 * D), device=dev, dtype=ad),
-                  vt=torch.empty((B, D, ops._round_up(L, 8)), device=dev, dtype=ad),
+                  vt=torch.empty((B, D, ldv), device=dev, dtype=ad),
                   o=torch.empty((B, L, D), device=dev, dtype=ad),
                   cat=torch.empty((B, L, D + mlp), device=dev, dtype=ad))
         if ops.precise():       # two-term split forms of the operands that to_out / to_add_out / proj_out read (policy dependent)
@@ -356,6 +370,9 @@ class FluxTransformer2DModel(ModelMixin, _Cached):
                 ws["o2"] = torch.empty((B, L, 2 * D), device=dev, dtype=ad)
             if any(b.proj_out.in_split() == 2 for b in self.single_transformer_blocks):
                 ws["cat2"] = torch.empty((B, L, 2 * (D + mlp)), device=dev, dtype=ad)
+        if fp8_attn:            # the MXFP8 operands of the fp8 attention blocks: q | k from RMSNorm + RoPE, V^T from its quantiser
+            ws["qk8"] = ops.Mxfp8(torch.empty((B, L, 2 * D), device=dev, dtype=torch.uint8), torch.empty((B, L, 2 * D // 32), device=dev, dtype=torch.uint8))
+            ws["vt8"] = ops.Mxfp8(torch.empty((B, D, ldv), device=dev, dtype=torch.uint8), torch.empty((B, D, ldv // 32), device=dev, dtype=torch.uint8))
         if ws["vt"].shape[-1] != L:
             ws["vt"].zero_()
         h = self.x_embedder.nhwc(x_tok)                                                   # [B, Li, D]

@@ -513,9 +513,10 @@ class Mxfp8:
         return Mxfp8(self.codes.reshape(*lead, self.codes.shape[-1]), self.scales.reshape(*lead, self.scales.shape[-1]))
 
 
-def quantize_mxfp8(x: torch.Tensor) -> Mxfp8:
+def quantize_mxfp8(x: torch.Tensor, out: Optional[Mxfp8] = None) -> Mxfp8:
     """x bf16 or fp32 [..., K] (K % 128 == 0) -> its OMGSR_EL_MXFP8 form, on the device (omgsr_quantize_mxfp8): scale = max(0, biased
-    exponent of the block's largest |v| - 8), code = (v / 2^(scale - 127)).clamp(-448, 448) in e4m3fn, round to nearest even."""
+    exponent of the block's largest |v| - 8), code = (v / 2^(scale - 127)).clamp(-448, 448) in e4m3fn, round to nearest even.
+    out: a dense Mxfp8 of x's shape to write into (a workspace)."""
     if x.dtype not in (torch.bfloat16, torch.float32):
         raise TypeError(f"quantize_mxfp8: expected bfloat16 or float32, got {x.dtype}")
     _req(x, x.dtype, "x")
@@ -523,8 +524,13 @@ def quantize_mxfp8(x: torch.Tensor) -> Mxfp8:
     if K % 128:
         raise ValueError(f"quantize_mxfp8: K = {K} is not a multiple of 128")
     rows = x.numel() // K
-    codes = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-    scales = torch.empty((*x.shape[:-1], K // 32), device=x.device, dtype=torch.uint8)
+    if out is not None:
+        if out.codes.shape != x.shape or out.scales.shape != (*x.shape[:-1], K // 32) or not (out.codes.is_contiguous() and out.scales.is_contiguous()):
+            raise ValueError("quantize_mxfp8: `out` does not match x")
+        codes, scales = out.codes, out.scales
+    else:
+        codes = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+        scales = torch.empty((*x.shape[:-1], K // 32), device=x.device, dtype=torch.uint8)
     check(_lib.load().omgsr_quantize_mxfp8(x.data_ptr(), EL_F32 if x.dtype == torch.float32 else EL_16, rows, K, K, codes.data_ptr(),
                                            scales.data_ptr(), _stream()), "omgsr_quantize_mxfp8")
     return Mxfp8(codes, scales)
@@ -1222,7 +1228,16 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, he
     (a projection written with out_split = 2); the scores then run three MFMA passes and, with p_split, the probabilities two (attn_split()).
     (an operand for the output projection; out_split 2: [B, Lq, 2*heads*D] as the two-term split; 3: the same bytes per row in the
     mixed-precision form OMGSR_EL_MX, for an output projection that runs as an MX GEMM).
-    Bk == 1 broadcasts one K/V over the batch (constant cross-attention context)."""
+    Bk == 1 broadcasts one K/V over the batch (constant cross-attention context).
+    q, k and vt may instead all be Mxfp8 (the fp8 tier's `fp8_attention`, head_dim 128, bf16 compute type): codes with the layouts above
+    (columns in bytes), vt [Bk, heads*D, ld] with ld % 128 == 0 quantised along the key index; the output is bf16 (out_split 1)."""
+    mx = [isinstance(x, Mxfp8) for x in (q, k, vt)]
+    if any(mx):
+        if not all(mx):
+            raise ValueError("attention: q, k and vt are all MXFP8 or none is")
+        if out_split != 1 or q_lo_col is not None or k_lo_col is not None:
+            raise ValueError("attention: MXFP8 operands take a plain bf16 output and no two-term splits")
+        return _attention_mxfp8(q, k, vt, heads, head_dim, scale, q_col, k_col, Lk, out, o_col)
     _req(q, act_dtype(), "q"); _req(k, act_dtype(), "k"); _req(vt, act_dtype(), "vt")
     B, Lq = q.shape[0], q.shape[1]
     Bk = k.shape[0]
@@ -1262,6 +1277,49 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, he
     return out
 
 
+def _attention_mxfp8(q: Mxfp8, k: Mxfp8, vt: Mxfp8, heads: int, head_dim: int, scale: float, q_col: int, k_col: int, Lk: Optional[int],
+                     out: Optional[torch.Tensor], o_col: int) -> torch.Tensor:
+    """attention() on OMGSR_EL_MXFP8 q / k / V^T (mxfp8_attn_kernel, ABI v19)."""
+    if _PRECISE or _ACT != torch.bfloat16:
+        raise ValueError("MXFP8 attention needs the bf16 compute type (the fp8 tier)")
+    if head_dim != 128:
+        raise ValueError(f"MXFP8 attention needs head_dim 128, got {head_dim}")
+    for name, t in (("q", q), ("k", k), ("vt", vt)):
+        _req(t.codes, torch.uint8, name); _req(t.scales, torch.uint8, name + " scales")
+        if t.codes.dim() != 3 or t.scales.shape != (*t.codes.shape[:-1], t.codes.shape[-1] // 32):
+            raise ValueError(f"attention: {name} is not an [B, rows, ld] MXFP8 operand")
+    if q_col % 128 or k_col % 128:
+        raise ValueError("attention: MXFP8 q / k columns must be multiples of 128")
+    B, Lq = q.codes.shape[0], q.codes.shape[1]
+    Bk = k.codes.shape[0]
+    Lk = Lk if Lk is not None else k.codes.shape[1]
+    inner = heads * head_dim
+    ld = vt.codes.shape[-1]
+    if vt.codes.shape[1] != inner:
+        raise ValueError(f"attention: vt has {vt.codes.shape[1]} rows, expected {inner}")
+    if ld % 128 or ld < Lk:
+        raise ValueError(f"attention: an MXFP8 V^T needs ld % 128 == 0 and ld >= Lk, got ld {ld} for Lk {Lk}")
+    if out is None:
+        out = torch.empty((B, Lq, inner), device=q.codes.device, dtype=torch.bfloat16)
+    _req(out, torch.bfloat16, "out")
+    bcast = Bk == 1 and B > 1
+    a = AttnArgs()
+    a.qkv_el = EL_MXFP8
+    a.q, a.k, a.vt = q.codes.data_ptr() + q_col, k.codes.data_ptr() + k_col, vt.codes.data_ptr()
+    a.q_scale, a.k_scale, a.vt_scale = q.scales.data_ptr() + q_col // 32, k.scales.data_ptr() + k_col // 32, vt.scales.data_ptr()
+    a.o = out.data_ptr() + o_col * 2
+    a.B, a.H, a.D, a.Lq, a.Lk = B, heads, head_dim, Lq, Lk
+    a.q_ld, a.k_ld, a.vt_ld, a.o_ld = q.codes.shape[-1], k.codes.shape[-1], ld, out.shape[-1]
+    a.q_sld, a.k_sld, a.vt_sld = q.scales.shape[-1], k.scales.shape[-1], vt.scales.shape[-1]
+    a.q_bstride, a.q_sbstride = Lq * a.q_ld, Lq * a.q_sld
+    a.k_bstride, a.k_sbstride = (0, 0) if bcast else (k.codes.shape[1] * a.k_ld, k.codes.shape[1] * a.k_sld)
+    a.vt_bstride, a.vt_sbstride = (0, 0) if bcast else (inner * ld, inner * a.vt_sld)
+    a.o_bstride = Lq * out.shape[-1]
+    a.scale = scale
+    check(_lib.load().omgsr_attention(C.byref(a), _stream()), "omgsr_attention")
+    return out
+
+
 def softmax_rows(s: torch.Tensor, valid: Optional[int] = None, split: bool = False) -> torch.Tensor:
     """softmax over the first `valid` columns of each row (the rest come out 0). split: [..., 2 L] rows [p_hi | p_lo] (the first factor of
     bmm_nt(both_split=True): the range-fallback tier's PV product)."""
@@ -1289,6 +1347,32 @@ def rmsnorm_rope_(x: torch.Tensor, w: torch.Tensor, cos: Optional[torch.Tensor],
     check(_lib.load().omgsr_rmsnorm_rope(x.data_ptr(), w.data_ptr(), _ptr(w_after), split_at, _ptr(cos), _ptr(sin), B, L, heads, head_dim, ld,
                                          col0, pos0, eps, _stream()), "omgsr_rmsnorm_rope")
     return x
+
+
+def rmsnorm_rope_mxfp8(x: torch.Tensor, w: torch.Tensor, cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], heads: int, head_dim: int,
+                       pos0: int = 0, eps: float = 1e-6, w_after: Optional[torch.Tensor] = None, split_at: int = 0,
+                       out: Optional[Mxfp8] = None) -> Mxfp8:
+    """rmsnorm_rope_ of the first heads * head_dim columns of x [B, L, ld] (bf16) with the fp32 result written as OMGSR_EL_MXFP8 (codes
+    [B, L, ld] bytes, scales [B, L, ld / 32]) instead of in place: quantize_mxfp8's rule on the fp32 values, no separate pass. x is unchanged.
+    out: a workspace of that shape."""
+    _req(x, torch.bfloat16, "x"); _req(w, torch.float32, "w")
+    if _PRECISE or _ACT != torch.bfloat16:
+        raise ValueError("rmsnorm_rope_mxfp8 needs the bf16 compute type (the fp8 tier)")
+    B, L, ld = x.shape
+    if ld % 128:
+        raise ValueError(f"rmsnorm_rope_mxfp8: row length {ld} is not a multiple of 128")
+    if tuple(w.shape) != (heads, head_dim) or (w_after is not None and tuple(w_after.shape) != (heads, head_dim)):
+        raise ValueError(f"rmsnorm_rope_mxfp8: w must be [{heads}, {head_dim}], got {tuple(w.shape)}")
+    if cos is not None and (cos.shape[0] < pos0 + L or sin.shape[0] < pos0 + L or cos.shape[-1] != head_dim):
+        raise ValueError(f"rmsnorm_rope_mxfp8: rope tables {tuple(cos.shape)} do not cover positions {pos0}..{pos0 + L - 1} x {head_dim}")
+    if out is None:
+        out = Mxfp8(torch.empty((B, L, ld), device=x.device, dtype=torch.uint8), torch.empty((B, L, ld // 32), device=x.device, dtype=torch.uint8))
+    elif out.codes.shape != (B, L, ld) or out.scales.shape != (B, L, ld // 32) or not (out.codes.is_contiguous() and out.scales.is_contiguous()):
+        raise ValueError("rmsnorm_rope_mxfp8: `out` does not match x")
+    check(_lib.load().omgsr_rmsnorm_rope_mxfp8(x.data_ptr(), w.data_ptr(), _ptr(w_after), split_at, _ptr(cos), _ptr(sin), B, L, heads, head_dim,
+                                               ld, 0, pos0, eps, out.codes.data_ptr(), out.scales.data_ptr(), ld, ld // 32, _stream()),
+          "omgsr_rmsnorm_rope_mxfp8")
+    return out
 
 
 # --------------------------------------------------------------------------------------------

@@ -46,11 +46,17 @@ class OMGSR_F_Infer(torch.nn.Module):
         super().__init__()
         # weight_dtype=torch.float8_e4m3fn: the fp8 tier - the bf16 tier with the DiT's token linears as MXFP8 x MXFP8 GEMMs (precision.FLUX_FP8;
         # precision_policy={"flux": {"fp8": [patterns]}} narrows the list). Modules are held and LoRA-merged in bf16, their fp8 forms packed lazily.
+        # precision_policy={"flux": {"fp8_attention": True | [block patterns]}} (fp8 tier only, opt-in) also runs those blocks' joint attention
+        # on MXFP8 q / k / V^T (precision.set_fp8_attention).
         fp8 = weight_dtype == torch.float8_e4m3fn
         if fp8 and precision_policy is not None and not (isinstance(precision_policy, dict) and set(precision_policy) <= {"flux"} and
-                                                         set(precision_policy.get("flux", {})) <= {"fp8"}):
-            raise ValueError("the fp8 tier's precision_policy is {'flux': {'fp8': [patterns]}} (a narrowing of precision.FLUX_FP8)")
+                                                         set(precision_policy.get("flux", {})) <= {"fp8", "fp8_attention"}):
+            raise ValueError("the fp8 tier's precision_policy is {'flux': {'fp8': [patterns], 'fp8_attention': True | [block patterns]}}")
+        if not fp8:
+            from ..precision import refuse_fp8_attention
+            refuse_fp8_attention(precision_policy, f"the {weight_dtype} tier")
         fp8_patterns = (precision_policy or {}).get("flux", {}).get("fp8") if fp8 else None
+        fp8_attention = (precision_policy or {}).get("flux", {}).get("fp8_attention") if fp8 else None
         weight_dtype = torch.bfloat16 if fp8 else weight_dtype
         ops.set_compute_dtype(weight_dtype)       # --weight_dtype picks the tier (bf16 | fp16 fast, fp32 accurate: see OMGSR_S_Infer)
         if vae is None:
@@ -77,11 +83,15 @@ class OMGSR_F_Infer(torch.nn.Module):
         self.verbose = verbose
         from ..precision import RangeFallback
         self.fp8 = fp8
-        from ..precision import FLUX_FP8, clear_fp8_linear, set_fp8_linear
+        from ..precision import FLUX_FP8, clear_fp8_attention, clear_fp8_linear, set_fp8_attention, set_fp8_linear
         if fp8:
             set_fp8_linear(self.flux_transformer, FLUX_FP8 if fp8_patterns is None else fp8_patterns)
         else:
             clear_fp8_linear(self.flux_transformer)
+        if fp8 and fp8_attention not in (None, False):
+            set_fp8_attention(self.flux_transformer, fp8_attention)
+        else:
+            clear_fp8_attention(self.flux_transformer)
         if weight_dtype == torch.float32:
             from ..precision import resolve
             resolve(precision_policy, vae=self.vae, flux=self.flux_transformer)

@@ -252,6 +252,61 @@ def clear_fp8_linear(model: nn.Module) -> None:
                 m.fp8 = False
 
 
+# The joint attention of a block in the fp8 tier (opt-in: precision_policy={"flux": {"fp8_attention": True | [block patterns]}}): q | k straight
+# out of RMSNorm + RoPE and V^T as OMGSR_EL_MXFP8, softmax(Q K^T) V on mxfp8_attn_kernel (ops.attention with Mxfp8 operands).
+_ATTN_BLOCK = re.compile(r"^(single_)?transformer_blocks\.\d+$")
+
+
+def _attn_blocks(model: nn.Module):
+    mods = dict(model.named_modules())
+    return [(name, mods[name + ".attn"]) for name in mods if _ATTN_BLOCK.match(name) and name + ".attn" in mods]
+
+
+def set_fp8_attention(model: nn.Module, patterns) -> int:
+    """Mark the attention of the FluxTransformer2DModel blocks whose names (`transformer_blocks.N`, `single_transformer_blocks.N`) match
+    `patterns` (a list of regular expressions, re.search; True = every block) as fp8 (FluxAttention.fp8); every other block's attention is
+    unmarked. ValueError for anything else than True or a list of strings, for a pattern that names no block, and outside the bf16 compute
+    type (the accurate tier, fp16). Returns how many blocks are marked."""
+    from . import ops
+    if ops.precise() or ops.act_dtype() != torch.bfloat16:
+        raise ValueError("fp8 attention needs the bf16 compute type (the fp8 tier); the accurate tier and fp16 have none")
+    if patterns is True:
+        patterns = [r"."]
+    elif not isinstance(patterns, (list, tuple)) or not all(isinstance(p, str) for p in patterns):
+        raise ValueError(f"fp8_attention is True or a list of block-name patterns, got {patterns!r}")
+    regs = [re.compile(p) for p in patterns]
+    blocks = _attn_blocks(model)
+    dead = [r.pattern for r in regs if not any(r.search(name) for name, _ in blocks)]
+    if dead:            # a typo would otherwise run the plain fp8 tier without a word
+        raise ValueError(f"fp8_attention patterns that name no block (transformer_blocks.N / single_transformer_blocks.N): {dead}")
+    _touch()
+    n = 0
+    for name, at in blocks:
+        at.fp8 = any(r.search(name) for r in regs)
+        n += at.fp8
+    return n
+
+
+def clear_fp8_attention(model: nn.Module) -> None:
+    """Unmark every fp8 attention of `model` (a pipeline of another tier, or the fp8 tier without the key, built on marked modules)."""
+    blocks = _attn_blocks(model)
+    if any(getattr(at, "fp8", False) for _, at in blocks):
+        _touch()
+        for _, at in blocks:
+            at.fp8 = False
+
+
+def fp8_attention_blocks(model: nn.Module) -> list:
+    """Names of the blocks whose attention runs in MXFP8."""
+    return [name for name, at in _attn_blocks(model) if getattr(at, "fp8", False)]
+
+
+def refuse_fp8_attention(policy, where: str) -> None:
+    """ValueError when a precision_policy asks for fp8 attention outside the fp8 tier."""
+    if isinstance(policy, dict) and any(isinstance(v, dict) and "fp8_attention" in v for v in policy.values()):
+        raise ValueError(f"fp8_attention belongs to OMGSR-F's fp8 tier (weight_dtype=torch.float8_e4m3fn), not to {where}")
+
+
 def fp8_layers(model: nn.Module) -> list:
     """Names of the fp8 Linear layers of `model`."""
     return [name for name, m in model.named_modules() if isinstance(m, Linear) and m.fp8]

@@ -7,6 +7,7 @@ fp32 CPU oracle and the bf16 HIP path start from bit-identical parameters.
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -106,3 +107,31 @@ def mxfp8_dequant(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     K = v.shape[-1]
     s = torch.exp2(scales.double() - 127)
     return (v.reshape(*v.shape[:-1], K // 32, 32) * s[..., None]).reshape(v.shape)
+
+
+def mxfp8_attention_ref(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, scale: float, Lk: Optional[int] = None, stats: Optional[dict] = None):
+    """Torch restatement of mxfp8_attn_kernel's arithmetic (attention_mxfp8.hip), in float64: q [..., Lq, D], k [..., >= Lk, D], vt [..., D, >= Lk]
+    are the DEQUANTISED operands (mxfp8_dequant). The keys are walked in the kernel's 64-key tiles with an exact running maximum; the
+    probabilities enter the PV product as e4m3(P 2^8) 2^-8 (round to nearest even), and the row sum adds those dequantised values. Keys >= Lk
+    are masked. stats (optional dict) receives the largest code value seen ("max_code")."""
+    Lk = k.shape[-2] if Lk is None else Lk
+    q, k, vt = q.double(), k.double(), vt.double()
+    sc = scale * math.log2(math.e)
+    m = torch.full(q.shape[:-1], -math.inf, dtype=torch.float64, device=q.device)
+    l = torch.zeros_like(m)
+    o = torch.zeros(*q.shape[:-1], vt.shape[-2], dtype=torch.float64, device=q.device)
+    top = 0.0
+    for k0 in range(0, Lk, 64):
+        k1 = min(k0 + 64, Lk)
+        s = q @ k[..., k0:k1, :].transpose(-1, -2)
+        m_new = torch.maximum(m, s.amax(-1))
+        alpha = torch.exp2((m - m_new) * sc)                                # m = -inf on the first tile: alpha = 0
+        o, l, m = o * alpha[..., None], l * alpha, m_new
+        p = torch.exp2((s - m[..., None]) * sc + 8.0)
+        pq = p.float().to(torch.float8_e4m3fn).double()                     # the code's value (P 2^8, in [0, 256])
+        top = max(top, float(pq.max()))
+        l = l + pq.sum(-1)
+        o = o + (pq @ vt[..., :, k0:k1].transpose(-1, -2)) * 2.0 ** -8
+    if stats is not None:
+        stats["max_code"] = top
+    return o / (l[..., None] * 2.0 ** -8)
