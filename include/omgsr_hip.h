@@ -463,7 +463,11 @@ int omgsr_timing_reset(void);
 /* kind: 1 igemm, 2 attention, 3 groupnorm, 4 layernorm, 5 elementwise, 6 softmax. variant (igemm only): which kernel
  * the dispatcher launched - 1 igemm_kernel (register staged), 2 igemm_dma_kernel, 3 igemm_halo_kernel, 4 igemm_dma_kernel
  * split-K + splitk_reduce_kernel, 5 igemm_p8_kernel, 6 igemm_halo_kernel in its phase-decomposed upsampling form, 7 / 8
- * igemm_halo_multi_kernel (several problems of one layer in one launch: nine-tap / phase-decomposed form), 18 mxfp8_gemm_kernel (ABI v18).
+ * igemm_halo_multi_kernel (several problems of one layer in one launch: nine-tap / phase-decomposed form), 9 igemm_gmx_kernel (GEMM over an
+ * OMGSR_EL_MX operand), 10 / 11 igemm_halo_kernel / igemm_halo_multi_kernel with the GroupNorm apply fused into the patch producer, 12 the halo
+ * kernel's split-K (chunk ranges as one igemm_halo_multi_kernel launch + splitk_reduce_kernel), 13 / 14 / 15 the halo kernel with fp6
+ * (OMGSR_EL_MX6) correction chunks: single, launch group, split-K, 16 / 17 the same in the phase-decomposed form: single, launch group,
+ * 18 mxfp8_gemm_kernel (ABI v18).
  * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;
