@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — OMGSR single-mid-timestep SR throughput on MI355X (see BASELINE.json / BASELINE.md).
 
-    python bench.py --gpus N --steps K --warmup W [--workload s1024|s512|f1024] [--batch B] [--weight-dtype fp32|fp16|bf16] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload s1024|s512|f1024] [--batch B] [--weight-dtype fp32|fp16|bf16] [--dump-outputs DIR] [--full]
 
 One process per GPU. With the torchrun env (RANK / WORLD_SIZE ...) this process IS a rank; without it and N > 1 the
 parent launches `python -m torch.distributed.run --nproc-per-node N ...` on itself as a child BEFORE anything touches the
@@ -15,12 +15,15 @@ operands with fp32 accumulation, two-term split operands on the layers omgsr_amd
 north-star tolerance (rel-L2 <= 1e-3, PSNR >= 60 dB vs the fp32 reference path) and therefore the default; bf16 (the
 reference's default dtype) and fp16 are the fast tiers, reported in `fast_tiers` with their own parity.
 
-Extra legs (rank 0, N == 1):
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+`--full` adds the extra legs below, after the timed region (rank 0; `--no-<leg>` drops one of them):
   roofline      one additional, untimed step with per-launch HIP events on the launch stream (omgsr_timing_*): per kernel
                 (igemm_halo_kernel / igemm_dma_kernel / igemm_kernel / attn_kernel) algorithmic FLOPs / summed duration,
                 the §8(d) algorithmic figure of the whole workload, and a measured MFMA micro-benchmark peak
-  cpu_baseline  the fp32 CPU oracle (oracle/, "port") on ONE image of the same workload; also yields PSNR / rel-L2 of the
-                HIP output vs the oracle's output for that image
+  cpu_baseline  (N == 1) the fp32 CPU oracle (oracle/, "port") on ONE image of the same workload; also yields PSNR / rel-L2 of
+                the HIP output vs the oracle's output for that image
+  fast tiers    (N == 1, S workloads) short timed runs of the other tiers and of the range-fallback mode, with their parity
+  f1024, latency_b1  (N == 1, default s1024 workload) the OMGSR-F 256->1024 record and the batch-1 latency record
 """
 from __future__ import annotations
 
@@ -65,16 +68,19 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=0, help="images per GPU per step (0 = workload default)")
     ap.add_argument("--weight-dtype", default=os.environ.get("OMGSR_BENCH_DTYPE", "fp32"), choices=sorted(DTYPES),
                     help="tier: fp32 = accurate (meets the north-star tolerance; default), bf16 / fp16 = fast")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-fast-tiers", action="store_true", help="skip the short bf16 / fp16 legs")
     ap.add_argument("--no-tiled-vae", action="store_true", help="s1024 only: run the VAE untiled (the reference's shipped default)")
-    ap.add_argument("--no-f1024", action="store_true", help="default (s1024, 1 GPU) run only: skip the OMGSR-F 256->1024 record (`workloads.f1024`)")
-    ap.add_argument("--no-latency", action="store_true", help="default (s1024, 1 GPU) run only: skip the batch-1 latency record (`workloads.latency_ms_b1`: eager vs hipGraph replay)")
-    ap.add_argument("--traffic-file", default="", help="rocprofv3 PMC summary (tools/profile_summary.py) to take `roofline.traffic` from; "
-                                                       "default: the newest profiles/r*_traffic.json whose args match this run")
-    ap.add_argument("--cpu-runs", type=int, default=1, help="timed runs of the CPU oracle (median reported) after one warm-up on a 512^2 crop")
-    ap.add_argument("--all-tiers", action="store_true", help="also time the fp16 tier and the accurate tier with fp8 correction segments (detail file only)")
+    legs = ap.add_argument_group("extra legs", "off by default; --full runs them after the timed region")
+    legs.add_argument("--full", action="store_true",
+                      help="also run the roofline, cpu_baseline / parity, fast-tier, f1024 and batch-1 latency legs")
+    legs.add_argument("--no-cpu-baseline", action="store_true")
+    legs.add_argument("--no-roofline", action="store_true")
+    legs.add_argument("--no-fast-tiers", action="store_true", help="skip the short bf16 / fp16 legs")
+    legs.add_argument("--no-f1024", action="store_true", help="default (s1024, 1 GPU) run only: skip the OMGSR-F 256->1024 record (`workloads.f1024`)")
+    legs.add_argument("--no-latency", action="store_true", help="default (s1024, 1 GPU) run only: skip the batch-1 latency record (`workloads.latency_ms_b1`: eager vs hipGraph replay)")
+    legs.add_argument("--traffic-file", default="", help="rocprofv3 PMC summary (tools/profile_summary.py) to take `roofline.traffic` from; "
+                                                         "default: the newest profiles/r*_traffic.json whose args match this run")
+    legs.add_argument("--cpu-runs", type=int, default=1, help="timed runs of the CPU oracle (median reported) after one warm-up on a 512^2 crop")
+    legs.add_argument("--all-tiers", action="store_true", help="also time the fp16 tier and the accurate tier with fp8 correction segments (detail file only)")
     ap.add_argument("--detail-file", default=os.environ.get("OMGSR_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json")),
                     help="where the full record goes (per-kernel tables, every tier, f1024 / latency records); the stdout line stays compact")
     ap.add_argument("--dry-run-cpu", action="store_true",
@@ -304,9 +310,10 @@ def main():
     images = B * world * args.steps
     value = images / elapsed
 
-    # Everything below is reporting. The timed region above is final; each extra leg runs under `guarded`, which records an error
-    # string instead of losing the line, and the stdout line is COMPACT (compact_line: <= 6 KB) - the full record
-    # (per-kernel tables, every tier, the f1024 / latency records) goes to --detail-file.
+    # Everything below is reporting. The timed region above is final; the extra legs run only under --full, each under `guarded`,
+    # which records an error string instead of losing the line, and the stdout line is COMPACT (compact_line:
+    # <= 6 KB) - the full record (per-kernel tables, every tier, the f1024 / latency records) goes to --detail-file.
+    extra_legs = rank == 0 and args.full
     errors = {}
 
     def guarded(name, fn, *a, **kw):
@@ -322,13 +329,13 @@ def main():
             return None
 
     roofline, extra = None, {}
-    if rank == 0 and not args.no_roofline:
+    if extra_legs and not args.no_roofline:
         r = guarded("roofline", roofline_leg, _lib, step, args, tflop_per_img, B, world, elapsed, tiled_vae, wdtype)
         if r is not None:
             roofline, extra = r
 
     cpu_baseline, parity = None, None
-    if rank == 0 and world == 1 and family == "S":
+    if extra_legs and world == 1 and family == "S":
         oracle_img = None
         if not args.no_cpu_baseline:
             r = guarded("cpu_baseline", cpu_leg, inp, out[:1], tile, overlap, side, tiled_vae, runs=args.cpu_runs)
@@ -348,13 +355,13 @@ def main():
             extra["other_tiers"] = {k: v for k, v in others.items() if v is not None}
             ops.set_compute_dtype(wdtype)
 
-    if rank == 0 and world == 1 and family == "F" and not args.no_cpu_baseline:
+    if extra_legs and world == 1 and family == "F" and not args.no_cpu_baseline:
         r = guarded("cpu_baseline", cpu_leg_f, device, [args.weight_dtype], side, tile, overlap)
         if r is not None:
             cpu_baseline, parity = r[0], r[1][args.weight_dtype]
 
     workloads = None
-    if rank == 0 and world == 1 and args.workload == "s1024" and not (args.no_f1024 and args.no_latency):
+    if extra_legs and world == 1 and args.workload == "s1024" and not (args.no_f1024 and args.no_latency):
         del pipe, step, out
         torch.cuda.empty_cache()
         workloads = {}
@@ -382,7 +389,7 @@ def main():
             "roofline": roofline, "cpu_baseline": cpu_baseline, "parity": parity,
             "per_rank_ms_per_step": {"min": round(fastest / args.steps * 1e3, 3), "max": round(elapsed / args.steps * 1e3, 3)},
             "n_ranks_seen": ranks_seen, "broadcast_bytes": int(moved),
-            "setup_s": round(build_secs, 1), **extra,
+            "setup_s": round(build_secs, 1), "full": args.full, **extra,
         }
         if workloads:
             full["workloads"] = workloads
@@ -463,7 +470,7 @@ def compact_line(full, family, side, B, tiled_vae, weight_dtype, detail_path, er
             also[f"s512_b1_{key}"] = _pick(lat[key], "eager_ms", "graph_ms", "graph_equals_eager_bitwise")
     if also:
         line["also"] = also
-    line.update(_pick(full, "per_rank_ms_per_step", "n_ranks_seen", "broadcast_bytes", "setup_s"))
+    line.update(_pick(full, "per_rank_ms_per_step", "n_ranks_seen", "broadcast_bytes", "setup_s", "full"))
     if errors:
         line["errors"] = {k: v[:160] for k, v in errors.items()}
     line["detail"] = detail_path

@@ -77,6 +77,15 @@ def test_steps_and_dump_outputs_arguments():
             b.parse(argv)
 
 
+def test_extra_legs_only_under_full():
+    """A plain run does only what the headline needs; the roofline, cpu_baseline, tier, f1024 and latency legs need --full and keep
+    their --no-<leg> switches there."""
+    b = _bench()
+    assert b.parse([]).full is False and b.parse(["--steps", "3", "--warmup", "1"]).full is False
+    a = b.parse(["--full", "--no-cpu-baseline", "--no-f1024"])
+    assert a.full and a.no_cpu_baseline and a.no_f1024 and not a.no_roofline
+
+
 def test_dump_outputs_is_exact_float32_and_a_fixed_sample_above_the_budget(tmp_path):
     """--dump-outputs: the step's output as float32 (bit-exact for every tier's dtype) when it fits the budget; above it, the same seeded
     sample of whole rows on every call, within the budget."""

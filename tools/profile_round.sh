@@ -7,7 +7,7 @@ TAG=${1:-r03}; shift || true
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fast-tiers --no-f1024 --no-latency --detail-file $OUT/bench_detail.json $*"
+BENCH="bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-fast-tiers --no-f1024 --no-latency --detail-file $OUT/bench_detail.json $*"
 OMGSR_KERNEL_TABLE=$OUT/ktable.md rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python3 $BENCH > $OUT/bench_under_trace.json 2> $OUT/trace.log
 DB=$(find $OUT/trace -name "*.db" | head -1)
 python tools/rocpd_summary.py $DB $OUT/kernel_stats.md > /dev/null

@@ -14,7 +14,7 @@ fam = traffic["families"]
 lines = []
 lines.append(f"# rocprofv3 --kernel-trace --stats of the default bench: {title}\n")
 lines.append(f"Command (GPU box, `tools/profile_round.sh`): `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 "
-             f"--no-cpu-baseline --no-fast-tiers --no-f1024 --no-latency{extra}`; config {json.dumps(bench['config'])}, dtype {bench['dtype']}. "
+             f"--full --no-cpu-baseline --no-fast-tiers --no-f1024 --no-latency{extra}`; config {json.dumps(bench['config'])}, dtype {bench['dtype']}. "
              f"5 pipeline passes in the trace (1 warm-up + 3 timed + 1 roofline pass).")
 lines.append(f"bench line under the profiler: {bench['ms_per_step']} ms/step ({bench['value']} {bench['unit']}). bench.py's HIP-event leg in the "
              f"same run: igemm family {roof['kernel_ms']} ms / {roof['launches']} launches; per kernel (total ms per pass, algorithmic TFLOP/s): "
