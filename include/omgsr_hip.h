@@ -298,7 +298,10 @@ int omgsr_transpose_split(const float* x, void* y, int32_t B, int32_t L, int32_t
  * k  bf16 rows [B][Lk]  with row stride k_ld
  * vt bf16 V TRANSPOSED: [B][H*D][vt_ld], key index contiguous (written by omgsr_igemm LAYOUT_T)
  * o  bf16 rows [B][Lq]  with row stride o_ld
- * D in {64, 128}; Lk arbitrary (keys >= Lk are masked); kv_bstride 0 broadcasts one K/V to all B.
+ * D in {64, 128, 512}; Lk arbitrary (keys >= Lk are masked); kv_bstride 0 broadcasts one K/V to all B.
+ * D = 512 (ABI v20, vae_attn_kernel: the VAE mid block's one-head attention, any H >= 1, no limit on Lk): 16-bit operands, o plain or the
+ * two-term split (o_lo_off), q / k plain or two-term splits (q_lo_off / k_lo_off, the D = 64 semantics); 16-byte aligned q / k / vt, 8-byte
+ * aligned o; p_split, vt_lo_off and o_mx return OMGSR_E_SHAPE. k rows and vt columns >= Lk are never used.
  */
 typedef struct omgsr_attn_args {
     const void* q; const void* k; const void* vt; void* o;
@@ -311,7 +314,7 @@ typedef struct omgsr_attn_args {
     int32_t o_mx;          /* 1: o is written in the mixed-precision operand form OMGSR_EL_MX (the output projection is an MX GEMM,
                               omgsr_igemm with mx_chunks16 > 0): a row of C = H*D channels is 4C bytes [hi fp16 | lo' fp8 | hi' fp8];
                               o_ld = 2C (16-bit slots), o_lo_off = 0, C % 64 == 0, fp16 compute type (ABI v14) */
-    int32_t q_lo_off;      /* ABI v17, with k_lo_off (both > 0 or both 0; D = 64): q and k are TWO-TERM SPLITS - the low halves of a row sit q_lo_off /
+    int32_t q_lo_off;      /* ABI v17, with k_lo_off (both > 0 or both 0; D = 64, and 512 from ABI v20): q and k are TWO-TERM SPLITS - the low halves of a row sit q_lo_off /
                               k_lo_off elements after q / k (a fused [q | k] projection written with out_lo_off: [q_hi | k_hi | q_lo | k_lo]); the
                               scores are K_hi Q_hi^T + K_lo Q_hi^T + K_hi Q_lo^T in one fp32 accumulator. The range-fallback tier's bf16 operands
                               (8-bit mantissas) need it to hold the north-star tolerance on the UNet (replaces nothing in torch: F.sdpa in fp32) */
@@ -343,8 +346,9 @@ typedef struct omgsr_attn_args {
 int omgsr_set_attention_defer_max(float log2_threshold);
 int omgsr_attention(const omgsr_attn_args* a, void* stream);
 
-/* Row softmax for the unfused d=512 VAE attention: p = softmax(s[:, :Lvalid]); s f32 [rows][L],
- * p bf16 [rows][L]; columns >= Lvalid (zero-padded keys) come out as exactly 0. */
+/* Row softmax for the materialised d=512 VAE attention (L <= 16384: the default path up to 128 x 128 latents, and the range-fallback tier,
+ * whose split P / split V^T the fused D = 512 kernel of omgsr_attention does not take): p = softmax(s[:, :Lvalid]); s f32 [rows][L],
+ * p bf16 [rows][L]; columns >= Lvalid (zero-padded keys) come out as exactly 0. L > 16384 returns OMGSR_E_SHAPE. */
 int omgsr_softmax_rows(const float* s, void* p, int64_t rows, int32_t L, int32_t Lvalid, void* stream);
 /* ABI v17: the same with the probabilities as a two-term split, p [rows][2 L] = [p_hi | p_lo] (range-fallback tier: the first factor of the
  * PV product, omgsr_igemm with in_ld = L and a [v_hi | v_hi | v_lo] second factor). */
@@ -468,7 +472,7 @@ int omgsr_timing_reset(void);
  * kernel's split-K (chunk ranges as one igemm_halo_multi_kernel launch + splitk_reduce_kernel), 13 / 14 / 15 the halo kernel with fp6
  * (OMGSR_EL_MX6) correction chunks: single, launch group, split-K, 16 / 17 the same in the phase-decomposed form: single, launch group,
  * 18 mxfp8_gemm_kernel (ABI v18).
- * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
+ * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19), 20 vae_attn_kernel (ABI v20, D = 512). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;
 int omgsr_timing_collect(omgsr_timing_entry* out, int cap);

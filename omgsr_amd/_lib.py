@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 from .build import lib_path
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class OmgsrError(RuntimeError):

@@ -1,4 +1,4 @@
-// Fused attention softmax(Q K^T * scale) V for gfx950, head_dim 64 / 128, bf16 in, fp32 softmax.
+// Fused attention softmax(Q K^T * scale) V for gfx950, head_dim 64 / 128 (512: attention_d512.hip), bf16 in, fp32 softmax.
 // Replaces F.scaled_dot_product_attention under diffusers' AttnProcessor2_0 / FluxAttnProcessor2_0
 // (UNet self/cross attention, Flux joint attention).
 //
@@ -500,6 +500,7 @@ int launch_attn(const omgsr_attn_args& a, hipStream_t st) {
 }  // namespace
 
 namespace omgsr { int mxfp8_attention(const omgsr_attn_args& a, hipStream_t st); }
+namespace omgsr { int vae_attention(const omgsr_attn_args& a, hipStream_t st, float defer); }
 
 extern "C" int omgsr_set_attention_defer_max(float log2_threshold) {
     if (!(log2_threshold >= 0.0f && log2_threshold <= 12.0f)) return OMGSR_E_BADARG;
@@ -515,6 +516,7 @@ extern "C" int omgsr_attention(const omgsr_attn_args* ap, void* stream) {
     if (a.qkv_el != OMGSR_EL_16) return OMGSR_E_BADARG;
     if ((a.q_ld & 7) || (a.k_ld & 7) || (a.vt_ld & 7) || (a.o_ld & 3) || a.vt_ld < a.Lk) return OMGSR_E_SHAPE;
     if (a.o_lo_off < 0 || (a.o_lo_off && ((a.o_lo_off & 3) || a.o_lo_off < a.H * a.D || a.o_ld < (int64_t)a.o_lo_off + a.H * a.D))) return OMGSR_E_SHAPE;
+    if (a.D == 512) return omgsr::vae_attention(a, (hipStream_t)stream, g_defer_max);                 // ABI v20: attention_d512.hip
     // MX output: the whole row belongs to this call (heads at column 0, o_ld = 2 H D slots), fp16 compute type
     if (a.o_mx && (a.o_lo_off || a.o_ld != 2ll * a.H * a.D || ((a.H * a.D) & 63) || omgsr::compute_dtype() != 1)) return OMGSR_E_SHAPE;
     // two-term split q / k (ABI v17): both or neither, 16-byte aligned low halves, head_dim 64 (the UNet's; FLUX's RMS-normalised q / k do not need it)

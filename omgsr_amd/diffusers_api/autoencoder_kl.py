@@ -8,10 +8,12 @@ attribute tree is the one infer/vaehook.py:296-329,340-355 duck-types (SURVEY.md
 Data layout: NCHW tensors at the API boundary (as diffusers), bf16 NHWC inside. GroupNorm+SiLU runs
 as a statistics pass + an apply pass feeding the implicit-GEMM conv; nearest-2x upsampling and the
 encoder's asymmetric pad are folded into the conv's gather; the d=512 single-head mid attention
-uses the batched-GEMM + masked row-softmax path.
+uses the batched-GEMM + masked row-softmax path up to 16384 tokens and the fused head_dim-512 kernel
+(ops.attention) past that, or wherever `VaeAttention.fused` / OMGSR_VAE_ATTN_FUSED asks for it.
 """
 from __future__ import annotations
 
+import os
 from types import SimpleNamespace
 from typing import Optional
 
@@ -99,9 +101,41 @@ class Upsample2D(nn.Module):
         return _nchw_call(self.nhwc, x, self.conv.out_channels)
 
 
+MATERIALISED_MAX_KEYS = 16384       # omgsr_softmax_rows: rows of at most 256 * 4 * 16 scores
+
+
+def _parse_fused_knob(value: Optional[str]) -> Optional[bool]:
+    """OMGSR_VAE_ATTN_FUSED: "1" = fused everywhere, "0" = materialised only, unset / anything else = automatic (None)."""
+    return {"0": False, "1": True}.get((value or "").strip())
+
+
+_ENV_FUSED = _parse_fused_knob(os.environ.get("OMGSR_VAE_ATTN_FUSED"))        # read once, at import (A/B runs)
+
+
+def vae_attention_route(L: int, precise: bool, attn_split: bool, switch: Optional[bool], env: Optional[bool] = None) -> str:
+    """"fused" | "materialised" for a VAE mid-block attention over L tokens. `switch` is the module's tri-state (VaeAttention.fused); when it
+    is None the environment knob `env` stands in. First match wins:
+      range-fallback tier (precise and attn_split)  materialised (it needs split P and split V^T), ValueError past 16384 keys
+      switch off                                    materialised (past 16384 keys the softmax kernel refuses the row)
+      switch on                                     fused
+      unset                                         materialised up to 16384 keys (unchanged default), fused past them"""
+    if precise and attn_split:
+        if L > MATERIALISED_MAX_KEYS:
+            raise ValueError(f"the range-fallback VAE attention is limited to {MATERIALISED_MAX_KEYS} keys (got {L}): its split probabilities "
+                             "and split V^T run on the materialised path only; tile the VAE or use the accurate tier's fp16 operands")
+        return "materialised"
+    if switch is None:
+        switch = env
+    if switch is not None:
+        return "fused" if switch else "materialised"
+    return "fused" if L > MATERIALISED_MAX_KEYS else "materialised"
+
+
 class VaeAttention(nn.Module):
     """diffusers Attention as built by the VAE mid block: 1 head of 512, GroupNorm, biased projections,
     residual connection."""
+
+    fused: Optional[bool] = None        # None: automatic (vae_attention_route); True / False: force the fused / materialised path
 
     def __init__(self, channels: int, groups: int):
         super().__init__()
@@ -142,8 +176,16 @@ class VaeAttention(nn.Module):
         # tier with single bf16 P / V here after the UNet's flash kernel had been fixed)
         full = ops.attn_split()
         qk2 = ops.precise() and (getattr(self, "qk_split", False) or full)
+        route = vae_attention_route(L, ops.precise(), full, self.fused, _ENV_FUSED)
         q = self.to_q.nhwc(g, out_dtype=ops.OUT_BF16, out_split=2 if qk2 else 1)
         k = self.to_k.nhwc(g, out_dtype=ops.OUT_BF16, out_split=2 if qk2 else 1)
+        if route == "fused":
+            # one launch of vae_attn_kernel: q (| q_lo) and k (| k_lo) as their projections wrote them, no scores or probabilities in HBM
+            vt = ops.linear_t(g, self.to_v.packed(), L)                           # [N, C, round_up(L, 8)]
+            o = ops.attention(q, k, vt, self.heads, Cc, self.scale, out_split=self.to_out[0].in_split(),
+                              q_lo_col=Cc if qk2 else None, k_lo_col=Cc if qk2 else None, p_split=False)
+            out = self.to_out[0].nhwc(o, residual=x.reshape(N, L, Cc), gn_groups=self.group_norm.num_groups)
+            return ops.carry_gn(out, out.reshape(N, H, W, Cc))
         if qk2:
             k = ops.split_rows_hhl(k, Lp)
         elif Lp != L:
@@ -348,6 +390,17 @@ class AutoencoderKL(ModelMixin):
         self.quant_conv = Conv2d(2 * c.latent_channels, 2 * c.latent_channels, 1) if c.use_quant_conv else None
         self.post_quant_conv = Conv2d(c.latent_channels, c.latent_channels, 1) if c.use_post_quant_conv else None
         self.posterior_noise: Optional[torch.Tensor] = None   # explicit eps [N,C,h,w] for parity runs
+
+    def set_fused_attention(self, mode: Optional[bool]) -> None:
+        """The mid-block attentions' path: None = automatic (materialised up to 16384 tokens, the fused head_dim-512 kernel past them),
+        True = fused at every size, False = materialised only (VaeAttention.fused)."""
+        if mode is not None and not isinstance(mode, bool):
+            raise ValueError("set_fused_attention: mode is None, True or False")
+        for m in self.modules():
+            if isinstance(m, VaeAttention):
+                m.fused = mode
+        from .. import precision
+        precision._touch()              # captured hipGraphs are keyed on the policy epoch (pipelines/graphed.py): never a stale replay
 
     # ---- fast NHWC entry points used by the pipelines -------------------------------------
     def encode_moments_nhwc(self, x_nhwc8: torch.Tensor) -> torch.Tensor:

@@ -1224,7 +1224,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, he
               o_col: int = 0, out_split: int = 1, o_lo_col: Optional[int] = None, q_lo_col: Optional[int] = None,
               k_lo_col: Optional[int] = None, p_split: bool = True) -> torch.Tensor:
     """q [B, Lq, *] (heads at columns q_col + h*D), k [Bk, Lk, *], vt [Bk, heads*D, ld] -> o [B, Lq, heads*D]
-    q_lo_col / k_lo_col (both or neither, head_dim 64): q and k are two-term splits whose low halves start at those columns of the same rows
+    head_dim 512 (the VAE mid block, any Lk): out_split 1 or 2, q_lo_col / k_lo_col with p_split=False, a single V^T.
+    q_lo_col / k_lo_col (both or neither, head_dim 64 or 512): q and k are two-term splits whose low halves start at those columns of the same rows
     (a projection written with out_split = 2); the scores then run three MFMA passes and, with p_split, the probabilities two (attn_split()).
     (an operand for the output projection; out_split 2: [B, Lq, 2*heads*D] as the two-term split; 3: the same bytes per row in the
     mixed-precision form OMGSR_EL_MX, for an output projection that runs as an MX GEMM).
@@ -1238,6 +1239,13 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, he
         if out_split != 1 or q_lo_col is not None or k_lo_col is not None:
             raise ValueError("attention: MXFP8 operands take a plain bf16 output and no two-term splits")
         return _attention_mxfp8(q, k, vt, heads, head_dim, scale, q_col, k_col, Lk, out, o_col)
+    if head_dim == 512:             # vae_attn_kernel (ABI v20): checked here, before the library is called
+        if out_split == 3:
+            raise ValueError("attention: head_dim 512 writes a plain or two-term-split output (out_split 1 or 2), not the MX form")
+        if vt.shape[1] == 2 * heads * head_dim:
+            raise ValueError("attention: head_dim 512 takes a single V^T; the two-term-split V^T is limited to head_dim 64")
+        if q_lo_col is not None and k_lo_col is not None and p_split:
+            raise ValueError("attention: head_dim 512 takes split q / k with p_split=False; split probabilities are limited to head_dim 64")
     _req(q, act_dtype(), "q"); _req(k, act_dtype(), "k"); _req(vt, act_dtype(), "vt")
     B, Lq = q.shape[0], q.shape[1]
     Bk = k.shape[0]
