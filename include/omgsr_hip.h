@@ -272,6 +272,32 @@ int omgsr_groupnorm_apply_shared(const void* x, void* y, const float* mean, cons
                                  const float* gamma, const float* beta, int32_t rows, int64_t HW, int32_t C,
                                  int32_t G, int32_t act, int32_t stat_rows, int32_t x_el, int32_t y_el, void* y2, int32_t y2_el,
                                  uint32_t* overflow_flag, void* stream);
+/* ABI v21: the same for up to OMGSR_GN_MAX_GROUPS tensors of one channel count that share statistics, affine, activation and
+ * element kinds (the tile-shape groups of a tiled-VAE layer) in ONE launch: the workgroup looks its group up in a prefix table of
+ * block counts. Group k is `rows` x `HW` pixels; y2 is set for every group or for none. Every element goes through the arithmetic of
+ * omgsr_groupnorm_apply_shared, so the bytes written equal those of one call per group. */
+typedef struct omgsr_gn_apply_group {
+    const void* x;
+    void* y;
+    void* y2;
+    int64_t HW;
+    int32_t rows;
+    int32_t reserved;
+} omgsr_gn_apply_group;
+int omgsr_groupnorm_apply_multi(const omgsr_gn_apply_group* groups, int32_t ngroups, const float* mean, const float* rstd,
+                                const float* gamma, const float* beta, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                int32_t x_el, int32_t y_el, int32_t y2_el, uint32_t* overflow_flag, void* stream);
+/* ABI v21: GroupNorm of the channel concatenation [a | b] of two fp32 stream tensors (Ca | Cb channels, Ca % 8 == 0) WITHOUT building it
+ * (the UNet's up path: decoder tensor | skip tensor).
+ * omgsr_groupnorm_finalize2: statistics from the PER-CHANNEL partials both producers left (partial_a [N][nslot_a][Ca][2], partial_b
+ * [N][nslot_b][Cb][2]; omgsr_igemm_gn_entries == Cout); groups of (Ca + Cb) / G channels may straddle the seam; count = HW * (Ca + Cb) / G.
+ * omgsr_groupnorm_apply2: omgsr_groupnorm_apply with x_el = OMGSR_EL_F32 whose input row is [xa row | xb row]; C = Ca + Cb. Same outputs
+ * (y, y2, overflow_flag), byte for byte, as omgsr_groupnorm_apply of the concatenated tensor with the same statistics. */
+int omgsr_groupnorm_finalize2(const float* partial_a, int32_t nslot_a, int32_t Ca, const float* partial_b, int32_t nslot_b, int32_t Cb,
+                              float* mean, float* rstd, float* var_out, int32_t N, int32_t G, double count, float eps, void* stream);
+int omgsr_groupnorm_apply2(const void* xa, const void* xb, int32_t Ca, void* y, const float* mean, const float* rstd, const float* gamma,
+                           const float* beta, int32_t N, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t y_el, void* y2, int32_t y2_el,
+                           uint32_t* overflow_flag, void* stream);
 
 /*
  * K9/K10 — LayerNorm over the last dim (replaces F.layer_norm and the AdaLN-Zero modulate chain of

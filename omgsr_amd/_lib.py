@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 from .build import lib_path
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class OmgsrError(RuntimeError):
@@ -51,6 +51,11 @@ class GnMergeArgs(C.Structure):
     _fields_ = [("partial", C.c_void_p * GN_MAX_GROUPS), ("count", C.c_double * GN_MAX_GROUPS),
                 ("weight", C.c_float * GN_MAX_GROUPS), ("tiles", C.c_int32 * GN_MAX_GROUPS),
                 ("nslot", C.c_int32 * GN_MAX_GROUPS), ("entries", C.c_int32 * GN_MAX_GROUPS), ("ngroups", C.c_int32)]
+
+
+class GnApplyGroup(C.Structure):
+    """One shape group of omgsr_groupnorm_apply_multi (omgsr_gn_apply_group)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p), ("HW", C.c_int64), ("rows", C.c_int32), ("reserved", C.c_int32)]
 
 
 class AttnArgs(C.Structure):
@@ -97,6 +102,9 @@ SIGNATURES = {
     "omgsr_groupnorm_partial": (C.c_int, [_P, _P, _I, _L, _I, _I, _I, _P]),
     "omgsr_groupnorm_finalize_merged": (C.c_int, [C.POINTER(GnMergeArgs), _P, _P, _P, _I, _I, _F, _P]),
     "omgsr_groupnorm_apply_shared": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "omgsr_groupnorm_apply_multi": (C.c_int, [C.POINTER(GnApplyGroup), _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "omgsr_groupnorm_finalize2": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, C.c_double, _F, _P]),
+    "omgsr_groupnorm_apply2": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _I, _P, _P]),
     "omgsr_image_to_model_input": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     "omgsr_colorfix_workspace_bytes": (C.c_int64, [_I, _I, _I, _I]),
     "omgsr_colorfix": (C.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),

@@ -100,17 +100,56 @@ __global__ void gn_finalize_kernel(const float* __restrict__ partial, float* __r
     if (var_out) var_out[i] = (float)v;
 }
 
+// pass 2 for the channel concatenation [a | b] of two tensors whose producers left PER-CHANNEL partials (a [N][nslot_a][Ca][2],
+// b [N][nslot_b][Cb][2]; slot counts and layouts differ, only the sum over all slots of an image is used): group g covers channels
+// [g cpg, (g + 1) cpg) of the concatenation and may straddle the seam at Ca. One wave per (n, g): lanes stride a's slots, then b's,
+// channels in increasing order inside a slot - a fixed order, double accumulation like gn_finalize_kernel. The UNet's up path: neither the
+// concatenated tensor nor a statistics read pass over it is needed.
+__global__ void gn_finalize2_kernel(const float* __restrict__ pa, const float* __restrict__ pb, float* __restrict__ mean, float* __restrict__ rstd,
+                                    float* __restrict__ var_out, int N, int G, int nslot_a, int nslot_b, int Ca, int Cb, double count, float eps) {
+    const int i = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int n = i / G, g = i - n * G;
+    const int cpg = (Ca + Cb) / G;
+    const int c0 = g * cpg, c1 = c0 + cpg;
+    const int a0 = c0 < Ca ? c0 : Ca, a1 = c1 < Ca ? c1 : Ca;                       // the group's channels of a: [a0, a1)
+    const int b0 = (c0 > Ca ? c0 : Ca) - Ca, b1 = (c1 > Ca ? c1 : Ca) - Ca;         // ... and of b: [b0, b1)
+    double s = 0.0, q = 0.0;
+    if (a1 > a0) {
+        for (int c = lane; c < nslot_a; c += 64) {
+            const float* p = pa + (((int64_t)n * nslot_a + c) * Ca) * 2;
+            for (int j = a0; j < a1; ++j) { s += (double)p[2 * j]; q += (double)p[2 * j + 1]; }
+        }
+    }
+    if (b1 > b0) {
+        for (int c = lane; c < nslot_b; c += 64) {
+            const float* p = pb + (((int64_t)n * nslot_b + c) * Cb) * 2;
+            for (int j = b0; j < b1; ++j) { s += (double)p[2 * j]; q += (double)p[2 * j + 1]; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
+    if (lane != 0) return;
+    const double m = s / count;
+    double v = q / count - m * m;
+    if (v < 0.0) v = 0.0;
+    mean[i] = (float)m;
+    rstd[i] = (float)(1.0 / sqrt(v + (double)eps));
+    if (var_out) var_out[i] = (float)v;
+}
+
 // GroupNorm apply (+ optional SiLU). grid = (nblk, N); each block builds the per-channel
 // (scale, shift) table of its image in LDS, then streams its pixel range.
+// (n, bx) = (row, block of the row's pixel range): blockIdx of the one-tensor kernels, looked up in the prefix table by the multi-group ones
 template <typename T>
-__global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
-                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows) {
+OMGSR_DEVINL void gn_apply_body(const T* __restrict__ x, T* __restrict__ y,
+                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows, const int n, const int bx) {
     extern __shared__ __attribute__((aligned(16))) float gn_lds[];
     float* sc = gn_lds;
     float* sh = gn_lds + C;
-    const int t = threadIdx.x, n = blockIdx.y;
+    const int t = threadIdx.x;
     const int ns = n % stat_rows;          // tiled VAE: rows are (tile, image) tile-major and share the image's statistics
     const int cpg = C / G;
     for (int c = t; c < C; c += 256) {
@@ -122,7 +161,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
     }
     __syncthreads();
     const int nch8 = C >> 3;
-    const int64_t p0 = (int64_t)blockIdx.x * px_per_block;
+    const int64_t p0 = (int64_t)bx * px_per_block;
     int64_t p1 = p0 + px_per_block; if (p1 > HW) p1 = HW;
     const int total = (int)((p1 - p0) * nch8);   // <= ~4k chunks per block by construction
     const T* xb = x + ((int64_t)n * HW + p0) * C;
@@ -166,18 +205,29 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
         c8 += step8; if (c8 >= nch8) c8 -= nch8;
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows) {
+    gn_apply_body<T>(x, y, mean, rstd, gamma, beta, HW, C, G, act, px_per_block, stat_rows, (int)blockIdx.y, (int)blockIdx.x);
+}
 
 // The same for the accurate tier's element kinds: fp32 stream input (XF32) and / or a two-term split operand output
 // (YEL = OMGSR_EL_SPLIT: hi at channel c, lo at channel C + c of a 2C-wide row). Chunk i of the block is (pixel, octet) =
 // (i / nch8, i % nch8), tracked incrementally.
 // Y2EL >= 0: a second output y2 = x itself as an MFMA operand (plain or two-term split), no affine / activation: the block's
 // 1x1 shortcut conv reads the same tensor this kernel already streams, so its cast costs a write and no extra read.
-template <typename T, bool XF32, int YEL, int Y2EL = -1>
-__global__ __launch_bounds__(256) void gn_apply_any_kernel(const void* __restrict__ x, void* __restrict__ y,
-                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows,
-                                                            void* __restrict__ y2 = nullptr, unsigned* __restrict__ ovf = nullptr) {
+// TWO: x is the channel concatenation [x | xb] of two fp32 stream tensors (Ca and C - Ca channels wide, Ca % 8 == 0) that is never
+// materialised: octets below Ca come from x, the rest from xb (the UNet's up path: decoder tensor | skip tensor). Everything after the
+// load is the one-source code, so the bytes written equal those of the concatenated tensor's pass.
+template <typename T, bool XF32, int YEL, int Y2EL, bool TWO = false>
+OMGSR_DEVINL void gn_apply_any_body(const void* __restrict__ x, void* __restrict__ y,
+                                    const float* __restrict__ mean, const float* __restrict__ rstd,
+                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                    int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows,
+                                    void* __restrict__ y2, unsigned* __restrict__ ovf, const int n, const int bx,
+                                    const void* __restrict__ xb = nullptr, const int Ca = 0) {
     extern __shared__ __attribute__((aligned(16))) float gn_lds[];
     float amax = 0.0f;          // fp16 range guard of the raw cast y2 (see omgsr_igemm_args.overflow_flag)
     auto note8 = [&](const float (&v)[8]) {
@@ -188,7 +238,7 @@ __global__ __launch_bounds__(256) void gn_apply_any_kernel(const void* __restric
     };
     float* sc = gn_lds;
     float* sh = gn_lds + C;
-    const int t = threadIdx.x, n = blockIdx.y;
+    const int t = threadIdx.x;
     const int ns = n % stat_rows;
     const int cpg = C / G;
     for (int c = t; c < C; c += 256) {
@@ -200,7 +250,7 @@ __global__ __launch_bounds__(256) void gn_apply_any_kernel(const void* __restric
     }
     __syncthreads();
     const int nch8 = C >> 3;
-    const int64_t p0 = (int64_t)blockIdx.x * px_per_block;
+    const int64_t p0 = (int64_t)bx * px_per_block;
     int64_t p1 = p0 + px_per_block; if (p1 > HW) p1 = HW;
     const int total = (int)((p1 - p0) * nch8);
     const int64_t pix0 = (int64_t)n * HW + p0;
@@ -234,14 +284,21 @@ __global__ __launch_bounds__(256) void gn_apply_any_kernel(const void* __restric
         if constexpr (Y2EL == 3) store8_mx<T>(y2, pix * 4 * C, C, cc8 * 8, v);
         else if constexpr (Y2EL >= 0) store8<T, Y2EL>(y2, pix * (Y2EL == 2 ? 2 * C : C) + cc8 * 8, C, v);
     };
+    auto get = [&](const int64_t pix, const int cc8, float (&v)[8]) {
+        if constexpr (TWO) {
+            static_assert(XF32, "two-source apply: fp32 stream tensors");
+            if (cc8 * 8 < Ca) load8<T, true>(x, pix * Ca + cc8 * 8, v);
+            else load8<T, true>(xb, pix * (C - Ca) + (cc8 * 8 - Ca), v);
+        } else load8<T, XF32>(x, pix * C + cc8 * 8, v);
+    };
     // two chunks (4 x 16-byte loads of an fp32 row) in flight per thread
     int i = t;
     for (; i + 256 < total; i += 512) {
         int c8b = c8, pxb = px;
         advance(c8b, pxb);
         float f[8], h[8];
-        load8<T, XF32>(x, (pix0 + px) * C + c8 * 8, f);
-        load8<T, XF32>(x, (pix0 + pxb) * C + c8b * 8, h);
+        get(pix0 + px, c8, f);
+        get(pix0 + pxb, c8b, h);
         if constexpr (Y2EL >= 0) {
             note8(f); note8(h);
             put2(pix0 + px, c8, f);
@@ -256,7 +313,7 @@ __global__ __launch_bounds__(256) void gn_apply_any_kernel(const void* __restric
     }
     for (; i < total; i += 256) {
         float f[8];
-        load8<T, XF32>(x, (pix0 + px) * C + c8 * 8, f);
+        get(pix0 + px, c8, f);
         if constexpr (Y2EL >= 0) { note8(f); put2(pix0 + px, c8, f); }
         transform(f, c8);
         put(pix0 + px, c8, f);
@@ -266,6 +323,62 @@ __global__ __launch_bounds__(256) void gn_apply_any_kernel(const void* __restric
         if (ovf && __any(amax > 65504.0f) && (t & 63) == 0) atomicOr(ovf, 1u);
         if (Y2EL == 3 && ovf && __any(amax > 448.0f) && (t & 63) == 0) atomicOr(ovf, 2u);     // MX twin: correction fields saturated (diagnostic bit)
     }
+}
+template <typename T, bool XF32, int YEL, int Y2EL = -1>
+__global__ __launch_bounds__(256) void gn_apply_any_kernel(const void* __restrict__ x, void* __restrict__ y,
+                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows,
+                                                            void* __restrict__ y2 = nullptr, unsigned* __restrict__ ovf = nullptr) {
+    gn_apply_any_body<T, XF32, YEL, Y2EL>(x, y, mean, rstd, gamma, beta, HW, C, G, act, px_per_block, stat_rows, y2, ovf, (int)blockIdx.y, (int)blockIdx.x);
+}
+template <typename T, int YEL, int Y2EL = -1>
+__global__ __launch_bounds__(256) void gn_apply_two_kernel(const void* __restrict__ xa, const void* __restrict__ xb, int Ca, void* __restrict__ y,
+                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows,
+                                                            void* __restrict__ y2, unsigned* __restrict__ ovf) {
+    gn_apply_any_body<T, true, YEL, Y2EL, true>(xa, y, mean, rstd, gamma, beta, HW, C, G, act, px_per_block, stat_rows, y2, ovf, (int)blockIdx.y, (int)blockIdx.x,
+                                                xb, Ca);
+}
+
+// Several tensors of one channel count that share statistics, affine, activation and element kinds in ONE launch (the tiled VAE keeps
+// corner / edge / interior tiles as separate dense tensors): an x-only grid, the workgroup looks its tensor up in a prefix table of block
+// counts (the way igemm_halo_multi_kernel does) and then runs the one-tensor body on its (row, pixel range) - the same arithmetic per element,
+// so the same bytes as a launch per tensor; the small groups no longer pay a kernel boundary and a partly filled round of workgroups each.
+struct GnApplyMulti {
+    const void* x[OMGSR_GN_MAX_GROUPS];
+    void* y[OMGSR_GN_MAX_GROUPS];
+    void* y2[OMGSR_GN_MAX_GROUPS];
+    int64_t HW[OMGSR_GN_MAX_GROUPS];
+    int64_t ppb[OMGSR_GN_MAX_GROUPS];
+    int nblk[OMGSR_GN_MAX_GROUPS];            // blocks per row
+    int start[OMGSR_GN_MAX_GROUPS + 1];       // first block of group k; start[count] = grid size
+    int count;
+};
+OMGSR_DEVINL int gn_multi_lookup(const GnApplyMulti& m, int& n, int& bx) {
+    int s = 0;
+    while (s + 1 < m.count && (int)blockIdx.x >= m.start[s + 1]) ++s;          // wave-uniform
+    const int local = (int)blockIdx.x - m.start[s];
+    n = local / m.nblk[s];
+    bx = local - n * m.nblk[s];
+    return s;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void gn_apply_multi_kernel(const GnApplyMulti m, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              int C, int G, int act, int stat_rows) {
+    int n, bx;
+    const int s = gn_multi_lookup(m, n, bx);
+    gn_apply_body<T>((const T*)m.x[s], (T*)m.y[s], mean, rstd, gamma, beta, m.HW[s], C, G, act, m.ppb[s], stat_rows, n, bx);
+}
+template <typename T, bool XF32, int YEL, int Y2EL = -1>
+__global__ __launch_bounds__(256) void gn_apply_any_multi_kernel(const GnApplyMulti m, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  int C, int G, int act, int stat_rows, unsigned* __restrict__ ovf) {
+    int n, bx;
+    const int s = gn_multi_lookup(m, n, bx);
+    gn_apply_any_body<T, XF32, YEL, Y2EL>(m.x[s], m.y[s], mean, rstd, gamma, beta, m.HW[s], C, G, act, m.ppb[s], stat_rows, m.y2[s], ovf, n, bx);
 }
 
 // (scale, shift) table of a GroupNorm for the conv kernels that normalise while they build their patch (omgsr_igemm_args.gn_scale_shift):
@@ -660,6 +773,55 @@ __global__ __launch_bounds__(256) void gn_finalize_merged_kernel(const omgsr_gn_
     if (var_out) var_out[i] = (float)vv;
 }
 
+// The same fold with the (group, tile) pairs spread over 16 waves per (n, g) instead of walked by 4: a pair's (mean, var) is computed exactly
+// as above and parked in LDS, then four threads add the weighted pairs of "their" old wave (pair & 3) in increasing pair order and thread 0
+// combines the four in wave order - the summation tree of gn_finalize_merged_kernel, so the same bits, at a quarter of the dependent
+// load chains per wave (the launch was 18 us of a mostly idle chip, 52 times per step). Up to GN_MERGE_WIDE_PAIRS pairs; more take the kernel above.
+constexpr int GN_MERGE_WIDE_PAIRS = 512, GN_MERGE_WIDE_WAVES = 16;
+__global__ __launch_bounds__(64 * GN_MERGE_WIDE_WAVES) void gn_finalize_merged_wide_kernel(const omgsr_gn_merge_args a, float* __restrict__ mean,
+                                                                                           float* __restrict__ rstd, float* __restrict__ var_out,
+                                                                                           int N, int G, float eps, int npairs) {
+    __shared__ double pm[GN_MERGE_WIDE_PAIRS], pv[GN_MERGE_WIDE_PAIRS], pw[GN_MERGE_WIDE_PAIRS];
+    __shared__ double red[4][2];
+    const int i = blockIdx.x, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = i / G, g = i - n * G;
+    for (int pair = wave; pair < npairs; pair += GN_MERGE_WIDE_WAVES) {
+        int k = 0, t = pair;
+        while (t >= a.tiles[k]) { t -= a.tiles[k]; ++k; }       // npairs = sum of tiles[0 .. ngroups): k stays below ngroups
+        const float* partial = a.partial[k];
+        const int nslot = a.nslot[k];
+        const int row = t * N + n;
+        double s = 0.0, q = 0.0;
+        const int entries = a.entries[k], epg = entries / G;
+        for (int c = lane; c < nslot; c += 64) {
+            const float* pp = partial + (((int64_t)row * nslot + c) * entries + g * epg) * 2;
+            for (int j = 0; j < epg; ++j) { s += (double)pp[2 * j]; q += (double)pp[2 * j + 1]; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
+        const double m = s / a.count[k];
+        double v = q / a.count[k] - m * m;
+        if (v < 0.0) v = 0.0;
+        if (lane == 0) { pm[pair] = m; pv[pair] = v; pw[pair] = (double)a.weight[k]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double m_acc = 0.0, v_acc = 0.0;
+        for (int pair = threadIdx.x; pair < npairs; pair += 4) {
+            m_acc += pw[pair] * pm[pair];
+            v_acc += pw[pair] * pv[pair];
+        }
+        red[threadIdx.x][0] = m_acc; red[threadIdx.x][1] = v_acc;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double mm = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+    const double vv = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    mean[i] = (float)mm;
+    rstd[i] = (float)(1.0 / sqrt(vv + (double)eps));
+    if (var_out) var_out[i] = (float)vv;
+}
+
 }  // namespace
 namespace {
 int gn_apply_launch(const void* x, void* y, const float* mean, const float* rstd, const float* gamma,
@@ -685,7 +847,13 @@ extern "C" int omgsr_groupnorm_finalize_merged(const omgsr_gn_merge_args* a, flo
     if (!a || !mean || !rstd || N <= 0 || G <= 0 || a->ngroups <= 0 || a->ngroups > OMGSR_GN_MAX_GROUPS) return OMGSR_E_BADARG;
     for (int k = 0; k < a->ngroups; ++k)
         if (!a->partial[k] || a->tiles[k] <= 0 || a->nslot[k] <= 0 || a->count[k] <= 0.0 || a->entries[k] < G || (a->entries[k] % G)) return OMGSR_E_BADARG;
-    hipLaunchKernelGGL(gn_finalize_merged_kernel, dim3(N * G), dim3(256), 0, (hipStream_t)stream, *a, mean, rstd, var_out, N, G, eps);
+    int npairs = 0;
+    for (int k = 0; k < a->ngroups; ++k) npairs += a->tiles[k];
+    static const char* narrow = getenv("OMGSR_GN_MERGE_NARROW");          // A/B runs: 1 = the four-wave kernel
+    if (npairs <= GN_MERGE_WIDE_PAIRS && !(narrow && narrow[0] == '1'))
+        hipLaunchKernelGGL(gn_finalize_merged_wide_kernel, dim3(N * G), dim3(64 * GN_MERGE_WIDE_WAVES), 0, (hipStream_t)stream, *a, mean, rstd, var_out, N, G, eps, npairs);
+    else
+        hipLaunchKernelGGL(gn_finalize_merged_kernel, dim3(N * G), dim3(256), 0, (hipStream_t)stream, *a, mean, rstd, var_out, N, G, eps);
     return (int)hipGetLastError();
 }
 
@@ -704,9 +872,42 @@ extern "C" int omgsr_groupnorm_apply(const void* x, void* y, const float* mean, 
 }
 
 namespace {
-int gn_apply_launch(const void* x, void* y, const float* mean, const float* rstd, const float* gamma,
-                    const float* beta, int32_t N, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows, int32_t x_el,
-                    int32_t y_el, void* y2, int32_t y2_el, uint32_t* ovf, void* stream) {
+// what an apply launch needs besides the element kinds: one tensor (multi == nullptr: grid (nblk, N)) or a table of them (x-only grid)
+struct GnApplyCtx {
+    const GnApplyMulti* multi;
+    dim3 grid;
+    size_t lds;
+    hipStream_t st;
+    const void* x; void* y; void* y2;
+    const float *mean, *rstd, *gamma, *beta;
+    int64_t HW, ppb;
+    int C, G, act, stat_rows;
+    uint32_t* ovf;
+    const void* xb; int Ca;          // xb != nullptr: the two-source form (fp32 stream tensors x | xb, Ca channels in x)
+};
+template <typename T, bool XF32, int YEL, int Y2EL = -1>
+void gn_any_go(const GnApplyCtx& c) {
+    if constexpr (XF32) {
+        if (c.xb) {
+            hipLaunchKernelGGL((gn_apply_two_kernel<T, YEL, Y2EL>), c.grid, dim3(256), c.lds, c.st, c.x, c.xb, c.Ca, c.y, c.mean, c.rstd, c.gamma, c.beta, c.HW, c.C,
+                               c.G, c.act, c.ppb, c.stat_rows, c.y2, c.ovf);
+            return;
+        }
+    }
+    if (c.multi) hipLaunchKernelGGL((gn_apply_any_multi_kernel<T, XF32, YEL, Y2EL>), c.grid, dim3(256), c.lds, c.st, *c.multi, c.mean, c.rstd, c.gamma, c.beta,
+                                    c.C, c.G, c.act, c.stat_rows, c.ovf);
+    else hipLaunchKernelGGL((gn_apply_any_kernel<T, XF32, YEL, Y2EL>), c.grid, dim3(256), c.lds, c.st, c.x, c.y, c.mean, c.rstd, c.gamma, c.beta, c.HW, c.C, c.G,
+                            c.act, c.ppb, c.stat_rows, c.y2, c.ovf);
+}
+template <typename T>
+void gn_plain_go(const GnApplyCtx& c) {
+    if (c.multi) hipLaunchKernelGGL(gn_apply_multi_kernel<T>, c.grid, dim3(256), c.lds, c.st, *c.multi, c.mean, c.rstd, c.gamma, c.beta, c.C, c.G, c.act, c.stat_rows);
+    else hipLaunchKernelGGL(gn_apply_kernel<T>, c.grid, dim3(256), c.lds, c.st, (const T*)c.x, (T*)c.y, c.mean, c.rstd, c.gamma, c.beta, c.HW, c.C, c.G, c.act,
+                            c.ppb, c.stat_rows);
+}
+
+int gn_apply_check(const void* x, void* y, const float* mean, const float* rstd, int32_t N, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t x_el,
+                   int32_t y_el, void* y2, int32_t y2_el) {
     if (!x || !y || !mean || !rstd || N <= 0 || HW <= 0 || C <= 0 || G <= 0) return OMGSR_E_BADARG;
     if ((x_el != OMGSR_EL_16 && x_el != OMGSR_EL_F32) || (y_el != OMGSR_EL_16 && y_el != OMGSR_EL_SPLIT && y_el != OMGSR_EL_MX && y_el != OMGSR_EL_MX6)) return OMGSR_E_BADARG;
     if ((y_el == OMGSR_EL_MX || y_el == OMGSR_EL_MX6) && ((C & 63) || omgsr::compute_dtype() != 1)) return OMGSR_E_SHAPE;        // fp16 compute type, whole 64-channel correction chunks
@@ -714,7 +915,11 @@ int gn_apply_launch(const void* x, void* y, const float* mean, const float* rstd
     if (y2 && y2_el == OMGSR_EL_MX && ((C & 63) || omgsr::compute_dtype() != 1)) return OMGSR_E_SHAPE;
     if ((C & 7) || (C % G) || C > 8192) return OMGSR_E_SHAPE;
     if (act != OMGSR_ACT_NONE && act != OMGSR_ACT_SILU) return OMGSR_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
+    return 0;
+}
+
+// pixels per block of an [N][HW][C] tensor
+int64_t gn_apply_ppb(int32_t N, int64_t HW, int32_t C) {
     // ~64 KB of activations per block keeps >= 2k blocks in flight on the big VAE maps
     static const char* ppe = getenv("OMGSR_GN_BLOCK_ELEMS");           // A/B runs
     static const int64_t belems = ppe ? atol(ppe) : 16384;
@@ -725,48 +930,112 @@ int gn_apply_launch(const void* x, void* y, const float* mean, const float* rstd
         ppb = (HW * N + 511) / 512;
         if (ppb < 8) ppb = 8;
     }
-    const int nblk = (int)((HW + ppb - 1) / ppb);
-    omgsr::TimingScope ts(OMGSR_TK_GN, 0.0, ((x_el == OMGSR_EL_F32 ? 4.0 : 2.0) + (y_el == OMGSR_EL_16 ? 2.0 : 4.0) +
-                                             (y2 ? (y2_el == OMGSR_EL_16 ? 2.0 : 4.0) : 0.0)) * N * (double)HW * C, st);
-    const size_t lds = 2 * C * sizeof(float);
-    const dim3 grid(nblk, N);
-#define OMGSR_GN_ANY2(YE, Y2) OMGSR_DISPATCH_T(hipLaunchKernelGGL((gn_apply_any_kernel<T, true, YE, Y2>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, y2, ovf))
-#define OMGSR_GN_ANY(XF, YE) OMGSR_DISPATCH_T(hipLaunchKernelGGL((gn_apply_any_kernel<T, XF, YE>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows))
+    return ppb;
+}
+
+double gn_apply_bytes(int32_t x_el, int32_t y_el, bool has_y2, int32_t y2_el) {
+    return (x_el == OMGSR_EL_F32 ? 4.0 : 2.0) + (y_el == OMGSR_EL_16 ? 2.0 : 4.0) + (has_y2 ? (y2_el == OMGSR_EL_16 ? 2.0 : 4.0) : 0.0);
+}
+
+// picks the instantiation for (x_el, y_el, y2_el); the element kinds were checked by gn_apply_check
+void gn_apply_dispatch(const GnApplyCtx& c, int32_t x_el, int32_t y_el, bool y2, int32_t y2_el) {
     if (y_el == OMGSR_EL_MX6) {              // fp6 correction thirds for a 3x3 conv of the halo-tile kernel (round 5); the twin keeps its own form
         using T = f16_t;
-#define OMGSR_GN_6(XF, Y2) hipLaunchKernelGGL((gn_apply_any_kernel<T, XF, 4, Y2>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, y2, ovf)
-        if (y2 && y2_el == OMGSR_EL_MX) OMGSR_GN_6(true, 3);
-        else if (y2 && y2_el == OMGSR_EL_SPLIT) OMGSR_GN_6(true, 2);
-        else if (y2) OMGSR_GN_6(true, 0);
-        else if (x_el == OMGSR_EL_F32) hipLaunchKernelGGL((gn_apply_any_kernel<T, true, 4>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, nullptr, nullptr);
-        else hipLaunchKernelGGL((gn_apply_any_kernel<T, false, 4>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, nullptr, nullptr);
-#undef OMGSR_GN_6
+        if (y2 && y2_el == OMGSR_EL_MX) gn_any_go<T, true, 4, 3>(c);
+        else if (y2 && y2_el == OMGSR_EL_SPLIT) gn_any_go<T, true, 4, 2>(c);
+        else if (y2) gn_any_go<T, true, 4, 0>(c);
+        else if (x_el == OMGSR_EL_F32) gn_any_go<T, true, 4>(c);
+        else gn_any_go<T, false, 4>(c);
     } else if (y2 && y2_el == OMGSR_EL_MX) {        // the shortcut's operand in the mixed-precision form (fp16 compute type)
         using T = f16_t;
-        if (y_el == OMGSR_EL_MX) hipLaunchKernelGGL((gn_apply_any_kernel<T, true, 3, 3>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, y2, ovf);
-        else if (y_el == OMGSR_EL_SPLIT) hipLaunchKernelGGL((gn_apply_any_kernel<T, true, 2, 3>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, y2, ovf);
-        else hipLaunchKernelGGL((gn_apply_any_kernel<T, true, 0, 3>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, y2, ovf);
+        if (y_el == OMGSR_EL_MX) gn_any_go<T, true, 3, 3>(c);
+        else if (y_el == OMGSR_EL_SPLIT) gn_any_go<T, true, 2, 3>(c);
+        else gn_any_go<T, true, 0, 3>(c);
     } else if (y_el == OMGSR_EL_MX) {
         using T = f16_t;
-        if (y2 && y2_el == OMGSR_EL_SPLIT) hipLaunchKernelGGL((gn_apply_any_kernel<T, true, 3, 2>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, y2, ovf);
-        else if (y2) hipLaunchKernelGGL((gn_apply_any_kernel<T, true, 3, 0>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, y2, ovf);
-        else if (x_el == OMGSR_EL_F32) hipLaunchKernelGGL((gn_apply_any_kernel<T, true, 3>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, nullptr, nullptr);
-        else hipLaunchKernelGGL((gn_apply_any_kernel<T, false, 3>), grid, dim3(256), lds, st, x, y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows, nullptr, nullptr);
+        if (y2 && y2_el == OMGSR_EL_SPLIT) gn_any_go<T, true, 3, 2>(c);
+        else if (y2) gn_any_go<T, true, 3, 0>(c);
+        else if (x_el == OMGSR_EL_F32) gn_any_go<T, true, 3>(c);
+        else gn_any_go<T, false, 3>(c);
     } else if (y2) {
-        if (y_el == OMGSR_EL_SPLIT && y2_el == OMGSR_EL_SPLIT) OMGSR_GN_ANY2(2, 2);
-        else if (y_el == OMGSR_EL_SPLIT) OMGSR_GN_ANY2(2, 0);
-        else if (y2_el == OMGSR_EL_SPLIT) OMGSR_GN_ANY2(0, 2);
-        else OMGSR_GN_ANY2(0, 0);
-    } else if (x_el == OMGSR_EL_F32 && y_el == OMGSR_EL_SPLIT) OMGSR_GN_ANY(true, 2);
-    else if (x_el == OMGSR_EL_F32) OMGSR_GN_ANY(true, 0);
-    else if (y_el == OMGSR_EL_SPLIT) OMGSR_GN_ANY(false, 2);
-    else OMGSR_DISPATCH_T(hipLaunchKernelGGL(gn_apply_kernel<T>, grid, dim3(256), lds, st, (const T*)x,
-                                             (T*)y, mean, rstd, gamma, beta, HW, C, G, act, ppb, stat_rows));
-#undef OMGSR_GN_ANY
-#undef OMGSR_GN_ANY2
+        if (y_el == OMGSR_EL_SPLIT && y2_el == OMGSR_EL_SPLIT) OMGSR_DISPATCH_T((gn_any_go<T, true, 2, 2>(c)));
+        else if (y_el == OMGSR_EL_SPLIT) OMGSR_DISPATCH_T((gn_any_go<T, true, 2, 0>(c)));
+        else if (y2_el == OMGSR_EL_SPLIT) OMGSR_DISPATCH_T((gn_any_go<T, true, 0, 2>(c)));
+        else OMGSR_DISPATCH_T((gn_any_go<T, true, 0, 0>(c)));
+    } else if (x_el == OMGSR_EL_F32 && y_el == OMGSR_EL_SPLIT) OMGSR_DISPATCH_T((gn_any_go<T, true, 2>(c)));
+    else if (x_el == OMGSR_EL_F32) OMGSR_DISPATCH_T((gn_any_go<T, true, 0>(c)));
+    else if (y_el == OMGSR_EL_SPLIT) OMGSR_DISPATCH_T((gn_any_go<T, false, 2>(c)));
+    else OMGSR_DISPATCH_T(gn_plain_go<T>(c));
+}
+
+int gn_apply_launch(const void* x, void* y, const float* mean, const float* rstd, const float* gamma,
+                    const float* beta, int32_t N, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows, int32_t x_el,
+                    int32_t y_el, void* y2, int32_t y2_el, uint32_t* ovf, void* stream) {
+    if (const int e = gn_apply_check(x, y, mean, rstd, N, HW, C, G, act, x_el, y_el, y2, y2_el)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t ppb = gn_apply_ppb(N, HW, C);
+    const int nblk = (int)((HW + ppb - 1) / ppb);
+    omgsr::TimingScope ts(OMGSR_TK_GN, 0.0, gn_apply_bytes(x_el, y_el, y2 != nullptr, y2_el) * N * (double)HW * C, st);
+    const GnApplyCtx c{nullptr, dim3(nblk, N), 2 * C * sizeof(float), st, x, y, y2, mean, rstd, gamma, beta, HW, ppb, C, G, act, stat_rows, y2 ? ovf : nullptr,
+                       nullptr, 0};
+    gn_apply_dispatch(c, x_el, y_el, y2 != nullptr, y2_el);
     return (int)hipGetLastError();
 }
 }  // namespace
+
+extern "C" int omgsr_groupnorm_finalize2(const float* partial_a, int32_t nslot_a, int32_t Ca, const float* partial_b, int32_t nslot_b, int32_t Cb,
+                                         float* mean, float* rstd, float* var_out, int32_t N, int32_t G, double count, float eps, void* stream) {
+    if (!partial_a || !partial_b || !mean || !rstd || N <= 0 || G <= 0 || nslot_a <= 0 || nslot_b <= 0 || Ca <= 0 || Cb <= 0 || count <= 0.0) return OMGSR_E_BADARG;
+    if ((Ca + Cb) % G) return OMGSR_E_SHAPE;
+    hipLaunchKernelGGL(gn_finalize2_kernel, dim3(N * G), dim3(64), 0, (hipStream_t)stream, partial_a, partial_b, mean, rstd, var_out, N, G, nslot_a, nslot_b, Ca, Cb,
+                       count, eps);
+    return (int)hipGetLastError();
+}
+
+extern "C" int omgsr_groupnorm_apply2(const void* xa, const void* xb, int32_t Ca, void* y, const float* mean, const float* rstd, const float* gamma,
+                                      const float* beta, int32_t N, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t y_el, void* y2, int32_t y2_el,
+                                      uint32_t* overflow_flag, void* stream) {
+    if (!xb || Ca <= 0 || Ca >= C || (Ca & 7)) return OMGSR_E_BADARG;
+    if (const int e = gn_apply_check(xa, y, mean, rstd, N, HW, C, G, act, OMGSR_EL_F32, y_el, y2, y2_el)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t ppb = gn_apply_ppb(N, HW, C);             // the block shape of the concatenated tensor's pass
+    const int nblk = (int)((HW + ppb - 1) / ppb);
+    omgsr::TimingScope ts(OMGSR_TK_GN, 0.0, gn_apply_bytes(OMGSR_EL_F32, y_el, y2 != nullptr, y2_el) * N * (double)HW * C, st);
+    const GnApplyCtx c{nullptr, dim3(nblk, N), 2 * C * sizeof(float), st, xa, y, y2, mean, rstd, gamma, beta, HW, ppb, C, G, act, N, y2 ? overflow_flag : nullptr,
+                       xb, Ca};
+    gn_apply_dispatch(c, OMGSR_EL_F32, y_el, y2 != nullptr, y2_el);
+    return (int)hipGetLastError();
+}
+
+extern "C" int omgsr_groupnorm_apply_multi(const omgsr_gn_apply_group* groups, int32_t ngroups, const float* mean, const float* rstd,
+                                           const float* gamma, const float* beta, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                           int32_t x_el, int32_t y_el, int32_t y2_el, uint32_t* overflow_flag, void* stream) {
+    if (!groups || ngroups <= 0 || ngroups > OMGSR_GN_MAX_GROUPS || stat_rows <= 0) return OMGSR_E_BADARG;
+    const bool has_y2 = groups[0].y2 != nullptr;
+    GnApplyMulti m{};
+    double elems = 0.0;
+    int64_t blocks = 0;
+    for (int k = 0; k < ngroups; ++k) {
+        const omgsr_gn_apply_group& g = groups[k];
+        if ((g.y2 != nullptr) != has_y2 || g.rows <= 0 || g.rows % stat_rows) return OMGSR_E_BADARG;
+        if (const int e = gn_apply_check(g.x, g.y, mean, rstd, g.rows, g.HW, C, G, act, x_el, y_el, g.y2, y2_el)) return e;
+        m.x[k] = g.x; m.y[k] = g.y; m.y2[k] = g.y2; m.HW[k] = g.HW;
+        m.ppb[k] = gn_apply_ppb(g.rows, g.HW, C);              // each group keeps the block shape of its own launch
+        m.nblk[k] = (int)((g.HW + m.ppb[k] - 1) / m.ppb[k]);
+        m.start[k] = (int)blocks;
+        blocks += (int64_t)m.nblk[k] * g.rows;
+        if (blocks >= (1ll << 31)) return OMGSR_E_SHAPE;
+        elems += (double)g.rows * (double)g.HW * C;
+    }
+    m.start[ngroups] = (int)blocks;
+    m.count = ngroups;
+    hipStream_t st = (hipStream_t)stream;
+    omgsr::TimingScope ts(OMGSR_TK_GN, 0.0, gn_apply_bytes(x_el, y_el, has_y2, y2_el) * elems, st);
+    const GnApplyCtx c{&m, dim3((unsigned)blocks), 2 * C * sizeof(float), st, nullptr, nullptr, nullptr, mean, rstd, gamma, beta, 0, 0, C, G, act, stat_rows,
+                       has_y2 ? overflow_flag : nullptr, nullptr, 0};
+    gn_apply_dispatch(c, x_el, y_el, has_y2, y2_el);
+    return (int)hipGetLastError();
+}
 
 namespace {
 template <bool XF32, int YEL>

@@ -51,7 +51,12 @@ class ResnetBlock2D(nn.Module):
         directly as its MFMA operand (no fp32 stream copy, no cast pass)."""
         # norm -> SiLU -> conv: the norm is handed to the conv (gn=): it runs as the conv's patch producer where the kernel can (a 16-bit
         # stream tensor into a plain 3x3 conv on the halo-tile kernel: every resnet conv of the fast tiers), as the apply pass otherwise
-        if self.conv_shortcut is not None and x.dtype == torch.float32:
+        if isinstance(x, tuple):
+            # accurate tier, UNet up path: x = (decoder tensor, skip tensor) stands for their channel concatenation, which only norm1 reads
+            # (apply -> conv1's operand, twin -> the shortcut's): it is not built where both producers left per-channel statistics
+            h, xc = self.norm1.nhwc_pair(x[0], x[1], ops.ACT_SILU, split=self.conv1.in_split(), also_cast=self.conv_shortcut.in_split())
+            h = self.conv1.nhwc(h, bias_override=conv1_bias, gn_groups=self.norm2.num_groups)
+        elif self.conv_shortcut is not None and x.dtype == torch.float32:
             # accurate tier: the 1x1 shortcut reads x itself; its operand copy is a second output of norm1's apply pass over x
             h, xc = self.norm1.nhwc(x, ops.ACT_SILU, split=self.conv1.in_split(), also_cast=self.conv_shortcut.in_split())
             h = self.conv1.nhwc(h, bias_override=conv1_bias, gn_groups=self.norm2.num_groups)

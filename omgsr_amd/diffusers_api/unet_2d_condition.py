@@ -316,12 +316,16 @@ class UNet2DConditionModel(ModelMixin):
             up = blk.upsamplers[0].conv if blk.upsamplers is not None else None
             for j, r in enumerate(blk.resnets):
                 last = up if j == len(blk.resnets) - 1 else None       # the block's last tensor feeds only the upsampling conv
-                h = ops.concat_channels(h, skips.pop())
+                skip = skips.pop()
+                if h.dtype == torch.float32 and r.conv_shortcut is not None:
+                    h = (h, skip)       # accurate tier: only norm1 reads the concatenation (ResnetBlock2D.nhwc, ops.group_norm_pair)
+                else:                   # 16-bit tiers: the concatenated tensor is itself the shortcut's operand
+                    h = ops.concat_channels(h, skip)
                 h = r.nhwc(h, fb[id(r)], out_for=last if blk.attentions is None else None)
                 if blk.attentions is not None:
                     h = blk.attentions[j].nhwc(h, ehs, out_for=last)
             if blk.upsamplers is not None:
-                h = blk.upsamplers[0].nhwc(h)
+                h = blk.upsamplers[0].nhwc(h, gn_groups=g if ops.precise() else 0)        # accurate tier: the next norm1 folds these with its skip's
         return self.conv_out.nhwc(h, gn=self.conv_norm_out.spec(h, ops.ACT_SILU))
 
     # ---- diffusers API ---------------------------------------------------------------------

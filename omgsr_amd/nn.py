@@ -203,6 +203,11 @@ class GroupNorm(nn.GroupNorm, _Packed):
         g, b = self._affine()
         return ops.group_norm(x, g, b, self.num_groups, self.eps, act, split=split, also_cast=also_cast)
 
+    def nhwc_pair(self, a, b, act=ops.ACT_NONE, split=1, also_cast=0):
+        """nhwc of the channel concatenation [a | b] without building it where ops.group_norm_pair can."""
+        g, bt = self._affine()
+        return ops.group_norm_pair(a, b, g, bt, self.num_groups, self.eps, act, split=split, also_cast=also_cast)
+
     def stats(self, x):
         return ops.group_norm_stats(x, self.num_groups, self.eps)
 
@@ -222,6 +227,11 @@ class GroupNorm(nn.GroupNorm, _Packed):
         if mean.shape[0] != x.shape[0]:       # tile-major rows sharing their image's statistics
             return ops.group_norm_apply_shared(x, mean, rstd, g, b, self.num_groups, act, split=split, also_cast=also_cast)
         return ops.group_norm_apply(x, mean, rstd, g, b, self.num_groups, act, split=split, also_cast=also_cast)
+
+    def apply_stats_multi(self, xs, mean, rstd, act=ops.ACT_NONE, split=1, also_cast=0):
+        """apply_stats over the tile-shape groups of a tiled-VAE layer in one launch (the same bytes as one call per group)."""
+        g, b = self._affine()
+        return ops.group_norm_apply_multi(xs, mean, rstd, g, b, self.num_groups, act, split=split, also_cast=also_cast)
 
     def forward(self, x):  # NCHW (or [B, C, L]) compat
         shp = x.shape

@@ -1178,6 +1178,31 @@ def group_norm_apply_shared(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Ten
     return (y, y2) if also_cast else y
 
 
+def group_norm_apply_multi(xs, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE, split: int = 1,
+                           also_cast: int = 0):
+    """group_norm_apply_shared over the tile-shape groups of one tiled-VAE layer in ONE launch: xs[k] is [T_k*N, h_k, w_k, C]
+    (tile-major), all of one channel count and element kind. Returns the list of y (of (y, y2) pairs with also_cast); the bytes are
+    those of one group_norm_apply_shared call per tensor."""
+    if not 0 < len(xs) <= _lib.GN_MAX_GROUPS:
+        raise ValueError(f"1 ... {_lib.GN_MAX_GROUPS} tile shape groups")
+    xel = _el(xs[0], "x")
+    Cc = xs[0].shape[-1]
+    if any(_el(x, "x") != xel or x.shape[-1] != Cc for x in xs):
+        raise ValueError("group_norm_apply_multi: one channel count and element kind per launch")
+    ys = [_operand_like(x, split) for x in xs]
+    y2s = [_cast_twin(x, xel, also_cast) for x in xs]
+    fused = bool(also_cast) and xel == EL_F32
+    desc = (_lib.GnApplyGroup * len(xs))()
+    for k, x in enumerate(xs):
+        desc[k].x, desc[k].y, desc[k].y2 = x.data_ptr(), ys[k].data_ptr(), (y2s[k].data_ptr() if fused else None)
+        desc[k].rows, desc[k].HW = x.shape[0], x.numel() // (x.shape[0] * Cc)
+    check(_lib.load().omgsr_groupnorm_apply_multi(desc, len(xs), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta), Cc, groups, act,
+                                                  mean.shape[0], xel, _el_of_split(split), _el_of_split(also_cast) if also_cast else EL_16,
+                                                  _ovf(xs[0].device) if fused else None, _stream()),
+          "omgsr_groupnorm_apply_multi")
+    return list(zip(ys, y2s)) if also_cast else ys
+
+
 def group_norm_apply(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: Optional[torch.Tensor],
                      beta: Optional[torch.Tensor], groups: int, act: int = ACT_NONE, inplace: bool = False, split: int = 1,
                      also_cast: int = 0):
@@ -1200,6 +1225,64 @@ def group_norm_apply(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, ga
 def group_norm(x: torch.Tensor, gamma, beta, groups: int, eps: float, act: int = ACT_NONE, split: int = 1, also_cast: int = 0):
     mean, rstd, _ = group_norm_stats(x, groups, eps)
     return group_norm_apply(x, mean, rstd, gamma, beta, groups, act, split=split, also_cast=also_cast)
+
+
+def _fused_gn_channels(x: torch.Tensor, N: int):
+    """The producer's partials when it left them PER CHANNEL ([N, nslot, C, 2]: they fold into any group boundary, whatever group count
+    the producer was told), else None. _fused_gn's validity rules otherwise."""
+    fused = getattr(x, "_omgsr_gn", None)
+    if fused is not None and fused[2] == x.data_ptr() and fused[3] == x._version and fused[0].shape[0] == N and fused[0].shape[2] == x.shape[-1]:
+        return fused[0]
+    return None
+
+
+def group_norm_pair_stats(a: torch.Tensor, b: torch.Tensor, groups: int, eps: float):
+    """(mean, rstd, var) [N, G] of the channel concatenation [a | b] from the per-channel partials both producers left, or None when
+    the pair does not qualify (see group_norm_pair)."""
+    N, Ca, Cb = a.shape[0], a.shape[-1], b.shape[-1]
+    if not (a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape[:-1] == b.shape[:-1] and Ca % 8 == 0 and Cb % 8 == 0
+            and (Ca + Cb) % groups == 0 and a.is_contiguous() and b.is_contiguous()):
+        return None
+    pa, pb = _fused_gn_channels(a, N), _fused_gn_channels(b, N)
+    if pa is None or pb is None:
+        return None
+    HW = a.numel() // (N * Ca)
+    mean = torch.empty((N, groups), device=a.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    var = torch.empty_like(mean)
+    check(_lib.load().omgsr_groupnorm_finalize2(pa.data_ptr(), pa.shape[1], Ca, pb.data_ptr(), pb.shape[1], Cb, mean.data_ptr(), rstd.data_ptr(),
+                                                var.data_ptr(), N, groups, float(HW) * ((Ca + Cb) // groups), eps, _stream()),
+          "omgsr_groupnorm_finalize2")
+    return mean, rstd, var
+
+
+def group_norm_apply_pair(a: torch.Tensor, b: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE,
+                          split: int = 1, also_cast: int = 0):
+    """group_norm_apply of the channel concatenation [a | b] of two fp32 stream tensors, read from the two tensors: the same bytes."""
+    _req(a, torch.float32, "a"); _req(b, torch.float32, "b")
+    N, Ca, Cb = a.shape[0], a.shape[-1], b.shape[-1]
+    if a.shape[:-1] != b.shape[:-1]:
+        raise ValueError("group_norm_apply_pair: a and b differ in more than the channel count")
+    HW = a.numel() // (N * Ca)
+    y = torch.empty((*a.shape[:-1], (Ca + Cb) * min(split, 2)), device=a.device, dtype=_ACT)
+    y2 = torch.empty((*a.shape[:-1], (Ca + Cb) * min(also_cast, 2)), device=a.device, dtype=_ACT) if also_cast else None
+    check(_lib.load().omgsr_groupnorm_apply2(a.data_ptr(), b.data_ptr(), Ca, y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta),
+                                             N, HW, Ca + Cb, groups, act, _el_of_split(split), _ptr(y2),
+                                             _el_of_split(also_cast) if also_cast else EL_16, _ovf(a.device) if also_cast else None, _stream()),
+          "omgsr_groupnorm_apply2")
+    return (y, y2) if also_cast else y
+
+
+def group_norm_pair(a: torch.Tensor, b: torch.Tensor, gamma, beta, groups: int, eps: float, act: int = ACT_NONE, split: int = 1, also_cast: int = 0):
+    """group_norm(concat_channels(a, b), ...) - the first GroupNorm of a UNet up-path resnet (decoder tensor | skip tensor). When both are
+    fp32 stream tensors whose producers left per-channel statistics, neither the concatenated tensor nor a statistics read pass over it
+    exists: the statistics fold from the two sets of partials and the apply pass reads the two tensors. Anything else - a 16-bit tier, a
+    producer that left nothing (a split-K conv, as on the 8x8 maps) or per-GROUP partials (reduced-size models with group sizes 2 / 4 / 8:
+    a group of the concatenation cannot be regrouped from those) - runs concat_channels + group_norm as before."""
+    st = group_norm_pair_stats(a, b, groups, eps)
+    if st is None:
+        return group_norm(concat_channels(a, b), gamma, beta, groups, eps, act, split=split, also_cast=also_cast)
+    return group_norm_apply_pair(a, b, st[0], st[1], gamma, beta, groups, act, split=split, also_cast=also_cast)
 
 
 # --------------------------------------------------------------------------------------------

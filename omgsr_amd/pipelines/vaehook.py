@@ -153,12 +153,16 @@ class VAEHook:
                         for k in groups:
                             res[k].append(op[4].nhwc(groups[k], pad=0))
                     continue
-                for k in groups:       # rows (tile, image) share the image's statistics
-                    if op[4] is not None:
-                        groups[k], xc = norm.apply_stats(groups[k], mean, rstd, act, split=op[3].in_split(), also_cast=op[4].in_split())
+                # rows (tile, image) share the image's statistics; every shape group in ONE apply launch, like the convs around it
+                keys = list(groups)
+                if op[4] is not None:
+                    outs = norm.apply_stats_multi([groups[k] for k in keys], mean, rstd, act, split=op[3].in_split(), also_cast=op[4].in_split())
+                    for k, (y, xc) in zip(keys, outs):
+                        groups[k] = y
                         res[k].append(op[4].nhwc(xc, pad=0))
-                    else:
-                        groups[k] = norm.apply_stats(groups[k], mean, rstd, act, split=op[3].in_split())
+                else:
+                    for k, y in zip(keys, norm.apply_stats_multi([groups[k] for k in keys], mean, rstd, act, split=op[3].in_split())):
+                        groups[k] = y
             elif kind == "conv":
                 keys = list(groups)
                 for k, y in zip(keys, op[1].nhwc_multi([groups[k] for k in keys], gn=pending, **op[2])):
