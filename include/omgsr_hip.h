@@ -202,6 +202,21 @@ int32_t omgsr_igemm_out_mx6_ok(const omgsr_igemm_args* a);
 int omgsr_groupnorm_scale_shift(const float* mean, const float* rstd, const float* gamma, const float* beta, float* out, int32_t nimg, int32_t C,
                                 int32_t G, void* stream);
 int omgsr_igemm(const omgsr_igemm_args* a, void* stream);
+/* ABI v22: MXFP8 x MXFP8 3x3 convolution (mxfp8_conv_kernel: the fp8 tier's opt-in VAE convs). The argument block of omgsr_igemm with
+ *   in        OMGSR_EL_MXFP8 codes  uint8 [N][H][W][Cin] (rows = pixels, K = Cin: what omgsr_quantize_mxfp8 / omgsr_groupnorm_apply_mxfp8 write)
+ *   in_scale  E8M0 [N][H][W][Cin / 32]
+ *   weight_cm codes uint8 [Cin / 64][9 taps][Cout_pad][64]: one MXFP8 block per 32 consecutive input channels of one (cout, ky, kx),
+ *             slice-major (tap = ky * 3 + kx; the 64 bytes are input channels 64 chunk .. + 63)
+ *   w_scale   E8M0 [Cin / 64][Cout_pad][2][16]: byte t < 9 of a 16-byte group = the scale of (cout, tap t, block 2 chunk + b); bytes 9-15 zero
+ *   weight    unused (NULL or weight_cm); K_pad = 9 Cin; mxf8 = 0 (that field keeps its GEMM-only meaning)
+ * and every output option of the 16-bit epilogue (bias, act, gate, residual, bf16 / fp32 out, gn_partial as omgsr_igemm_gn_slots / _gn_entries
+ * answer for the same block). Pixels outside the image contribute exact zeros whatever the planes hold.
+ * omgsr_conv_mxfp8_ok: 1 when the problem is served (pointers may still be unset) - 3x3 stride 1 pad 1, no upsampling, the geometry for which
+ * omgsr_igemm hands the bf16 problem to the halo-tile kernel's spatial nine-tap form (its tile-count policy included; one sample's rows in
+ * batch-invariant mode), Cin % 128 == 0, Cin <= 512, Cout >= 96, Cout_pad % 128 == 0, bf16 compute type, none of the split / MX / mxf8 /
+ * GroupNorm-producer / upsample / out_lo_off / out_mx fields. omgsr_conv_mxfp8 returns OMGSR_E_SHAPE for anything else (never another kernel). */
+int32_t omgsr_conv_mxfp8_ok(const omgsr_igemm_args* a);
+int omgsr_conv_mxfp8(const omgsr_igemm_args* a, void* stream);
 /* The problems of ONE layer that differ only in tensors and spatial extents (the tiled VAE runs every layer once per tile-shape group:
  * corner / edge / interior tiles are separate dense tensors; infer/vaehook.py:537-829 walks them one tile at a time). Call
  * omgsr_igemm_multi_plan first: it writes `group_tiles` into every problem, so that omgsr_igemm_gn_slots / _gn_entries /
@@ -293,6 +308,12 @@ int omgsr_groupnorm_apply_multi(const omgsr_gn_apply_group* groups, int32_t ngro
  * [N][nslot_b][Cb][2]; omgsr_igemm_gn_entries == Cout); groups of (Ca + Cb) / G channels may straddle the seam; count = HW * (Ca + Cb) / G.
  * omgsr_groupnorm_apply2: omgsr_groupnorm_apply with x_el = OMGSR_EL_F32 whose input row is [xa row | xb row]; C = Ca + Cb. Same outputs
  * (y, y2, overflow_flag), byte for byte, as omgsr_groupnorm_apply of the concatenated tensor with the same statistics. */
+/* ABI v22: omgsr_groupnorm_apply_shared whose fp32 result act((x - mean) rstd gamma + beta) is written in the OMGSR_EL_MXFP8 form, by
+ * omgsr_quantize_mxfp8's rule: codes uint8 [rows][HW][C], scales uint8 [rows][HW][C / 32] (the operand of omgsr_conv_mxfp8). x (bf16 or
+ * fp32 per x_el) is read only. C % 128 == 0, bf16 compute type. */
+int omgsr_groupnorm_apply_mxfp8(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma,
+                                const float* beta, int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                int32_t x_el, void* stream);
 int omgsr_groupnorm_finalize2(const float* partial_a, int32_t nslot_a, int32_t Ca, const float* partial_b, int32_t nslot_b, int32_t Cb,
                               float* mean, float* rstd, float* var_out, int32_t N, int32_t G, double count, float eps, void* stream);
 int omgsr_groupnorm_apply2(const void* xa, const void* xb, int32_t Ca, void* y, const float* mean, const float* rstd, const float* gamma,

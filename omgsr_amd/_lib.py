@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 from .build import lib_path
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 class OmgsrError(RuntimeError):
@@ -97,6 +97,9 @@ SIGNATURES = {
     "omgsr_igemm_gn_entries": (C.c_int32, [C.POINTER(IgemmArgs)]),
     "omgsr_igemm_gn_fusable": (C.c_int32, [C.POINTER(IgemmArgs)]),
     "omgsr_igemm_out_mx6_ok": (C.c_int32, [C.POINTER(IgemmArgs)]),
+    "omgsr_conv_mxfp8_ok": (C.c_int32, [C.POINTER(IgemmArgs)]),
+    "omgsr_conv_mxfp8": (C.c_int, [C.POINTER(IgemmArgs), _P]),
+    "omgsr_groupnorm_apply_mxfp8": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P]),
     "omgsr_groupnorm_scale_shift": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "omgsr_groupnorm_finalize": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, C.c_double, _F, _P]),
     "omgsr_groupnorm_partial": (C.c_int, [_P, _P, _I, _L, _I, _I, _I, _P]),

@@ -664,6 +664,40 @@ extern "C" int omgsr_igemm_multi(const omgsr_igemm_args* args, int32_t count, vo
     return flush();
 }
 
+// ---- ABI v22: MXFP8 x MXFP8 3x3 convolution (conv_mxfp8.hip) -----------------------------------------------------------------------
+namespace omgsr {
+bool mxfp8_conv_shape_ok(const omgsr_igemm_args& a);
+int mxfp8_conv_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, double flops);
+}
+namespace {
+// Served: what mxfp8_conv_kernel runs AND the geometry for which this dispatcher hands the bf16 problem to the halo-tile kernel's spatial
+// nine-tap form (tile-count policy included, one sample's rows in batch-invariant mode): the fp8 form replaces that launch, nothing else
+bool conv_mxfp8_ok(omgsr_igemm_args a) {
+    if (a.in_ld == a.Cin) a.in_ld = 0;
+    if (!omgsr::mxfp8_conv_shape_ok(a)) return false;
+    if (!a.weight_cm) a.weight_cm = &a;             // (the answer does not depend on the pointers: the host asks before it packs)
+    a.workspace = nullptr;
+    return use_halo(a) && !use_halo_phase(a) && omgsr::igemm_halo_flat(a) == 0;
+}
+}  // namespace
+
+extern "C" int32_t omgsr_conv_mxfp8_ok(const omgsr_igemm_args* ap) { return (ap && conv_mxfp8_ok(*ap)) ? 1 : 0; }
+
+extern "C" int omgsr_conv_mxfp8(const omgsr_igemm_args* ap, void* stream) {
+    if (!ap) return OMGSR_E_BADARG;
+    omgsr_igemm_args a = *ap;
+    if (!a.weight) a.weight = a.weight_cm;          // (the row-major packing does not exist in this form)
+    if (!a.in_scale || !a.w_scale || !a.weight_cm) return OMGSR_E_BADARG;
+    {
+        const int rc = validate_args(a);
+        if (rc != 0) return rc;
+    }
+    if (!conv_mxfp8_ok(a)) return OMGSR_E_SHAPE;
+    double flops, bytes;
+    work_of(a, &flops, &bytes);
+    return omgsr::mxfp8_conv_launch(a, geo_of(a), (hipStream_t)stream, flops);
+}
+
 extern "C" int omgsr_igemm(const omgsr_igemm_args* ap, void* stream) {
     if (!ap) return OMGSR_E_BADARG;
     omgsr_igemm_args a = *ap;

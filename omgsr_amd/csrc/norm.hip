@@ -693,6 +693,60 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_mxfp8_kernel(const bf16_t* _
     if ((sub & 3) == 0) scales[row * s_ld + col0 / 32 + h * (D / 32) + (sub >> 2)] = (unsigned char)s;
 }
 
+// GroupNorm apply (+ SiLU) with the fp32 result written as OMGSR_EL_MXFP8 codes + scales (the operand of omgsr_conv_mxfp8, ABI v22): the
+// arithmetic of gn_apply_any_body up to the rounding, then omgsr_quantize_mxfp8's rule. A thread holds one octet; C % 32 == 0 and 256 % 4 == 0
+// keep the four octets of a 32-channel block in one lane quad in every iteration, so the block maximum is two DPP exchanges.
+template <bool XF32>
+__global__ __launch_bounds__(256) void gn_apply_mxfp8_kernel(const void* __restrict__ x, unsigned char* __restrict__ codes, unsigned char* __restrict__ scales,
+                                                              const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows) {
+    extern __shared__ __attribute__((aligned(16))) float gn_lds[];
+    float* sc = gn_lds;
+    float* sh = gn_lds + C;
+    const int t = threadIdx.x, n = (int)blockIdx.y;
+    const int ns = n % stat_rows;
+    const int cpg = C / G;
+    for (int c = t; c < C; c += 256) {
+        const int g = c / cpg;
+        const float r = rstd[ns * G + g], m = mean[ns * G + g];
+        const float a = r * (gamma ? gamma[c] : 1.0f);
+        sc[c] = a;
+        sh[c] = (beta ? beta[c] : 0.0f) - m * a;
+    }
+    __syncthreads();
+    const int nch8 = C >> 3;
+    const int64_t p0 = (int64_t)blockIdx.x * px_per_block;
+    int64_t p1 = p0 + px_per_block; if (p1 > HW) p1 = HW;
+    const int total = (int)((p1 - p0) * nch8);
+    const int64_t pix0 = (int64_t)n * HW + p0;
+    const int step8 = 256 % nch8, stepp = 256 / nch8;
+    int c8 = t % nch8, px = t / nch8;
+    for (int i = t; i < total; i += 256) {
+        float f[8];
+        load8<bf16_t, XF32>(x, (pix0 + px) * C + c8 * 8, f);
+        const f32x4_t* sa = reinterpret_cast<const f32x4_t*>(sc + c8 * 8);
+        const f32x4_t* ha = reinterpret_cast<const f32x4_t*>(sh + c8 * 8);
+        const f32x4_t sa0 = sa[0], sa1 = sa[1], ha0 = ha[0], ha1 = ha[1];
+        float mx = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float v = f[e] * (e < 4 ? sa0[e & 3] : sa1[e & 3]) + (e < 4 ? ha0[e & 3] : ha1[e & 3]);
+            f[e] = (act == OMGSR_ACT_SILU) ? silu_f(v) : v;
+            mx = fmaxf(mx, fabsf(f[e]));
+        }
+        mx = quad_max(mx);
+        const int s = mxfp8_scale(mx);
+        u32x2_t out = {0u, 0u};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[e >> 2] |= mxfp8_code(f[e], s) << (8 * (e & 3));
+        *reinterpret_cast<u32x2_t*>(codes + (pix0 + px) * C + c8 * 8) = out;
+        if ((c8 & 3) == 0) scales[(pix0 + px) * (C >> 5) + (c8 >> 2)] = (unsigned char)s;
+        c8 += step8; px += stepp;
+        if (c8 >= nch8) { c8 -= nch8; ++px; }
+    }
+}
+
 }  // namespace
 
 extern "C" int omgsr_groupnorm_scale_shift(const float* mean, const float* rstd, const float* gamma, const float* beta, float* out, int32_t nimg,
@@ -982,6 +1036,25 @@ int gn_apply_launch(const void* x, void* y, const float* mean, const float* rstd
     return (int)hipGetLastError();
 }
 }  // namespace
+
+extern "C" int omgsr_groupnorm_apply_mxfp8(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma,
+                                           const float* beta, int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                           int32_t x_el, void* stream) {
+    if (!x || !codes || !scales || !mean || !rstd || rows <= 0 || HW <= 0 || C <= 0 || G <= 0 || stat_rows <= 0 || (rows % stat_rows)) return OMGSR_E_BADARG;
+    if ((x_el != OMGSR_EL_16 && x_el != OMGSR_EL_F32) || (act != OMGSR_ACT_NONE && act != OMGSR_ACT_SILU)) return OMGSR_E_BADARG;
+    if ((C % 128) || (C % G) || C > 8192 || omgsr::compute_dtype() != 0) return OMGSR_E_SHAPE;      // the format's K % 128; a 16-bit x is bf16
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t ppb = gn_apply_ppb(rows, HW, C);
+    const dim3 grid((unsigned)((HW + ppb - 1) / ppb), rows);
+    omgsr::TimingScope ts(OMGSR_TK_GN, 0.0, ((x_el == OMGSR_EL_F32 ? 4.0 : 2.0) + 1.0 + 1.0 / 32.0) * rows * (double)HW * C, st);
+    if (x_el == OMGSR_EL_F32)
+        hipLaunchKernelGGL(gn_apply_mxfp8_kernel<true>, grid, dim3(256), 2 * C * sizeof(float), st, x, (unsigned char*)codes, (unsigned char*)scales, mean, rstd, gamma,
+                           beta, HW, (int)C, (int)G, (int)act, ppb, (int)stat_rows);
+    else
+        hipLaunchKernelGGL(gn_apply_mxfp8_kernel<false>, grid, dim3(256), 2 * C * sizeof(float), st, x, (unsigned char*)codes, (unsigned char*)scales, mean, rstd, gamma,
+                           beta, HW, (int)C, (int)G, (int)act, ppb, (int)stat_rows);
+    return (int)hipGetLastError();
+}
 
 extern "C" int omgsr_groupnorm_finalize2(const float* partial_a, int32_t nslot_a, int32_t Ca, const float* partial_b, int32_t nslot_b, int32_t Cb,
                                          float* mean, float* rstd, float* var_out, int32_t N, int32_t G, double count, float eps, void* stream) {

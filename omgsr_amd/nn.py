@@ -135,6 +135,23 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
     # set by Upsample2D: this 3x3 conv is applied to a nearest-2x upsampled map, so its packed weight also carries the four
     # phase-summed 2 x 2 kernels (ops.pack_conv_weight upsample_phases) and runs with 4 / 9 of the MFMA work
     phase_upsample = False
+    # the fp8 tier (precision.set_fp8_conv): where the library serves the problem (ops.conv2d fp8_pack) this 3x3 conv runs as an MXFP8 x MXFP8
+    # convolution behind a GroupNorm apply pass that writes MXFP8. The bf16 pack stays (problems the kernel does not serve take it, exactly as
+    # without the mark); the MXFP8 form is packed lazily next to it, under a key of its own that names the form, so a weight edit re-packs both
+    fp8 = False
+
+    def packed_mxfp8(self) -> ops.PackedWeight:
+        k = _key(self.weight, self.bias, "mxfp8-conv")
+        if getattr(self, "_pk8_key", None) != k:
+            bump_cache_epoch()
+            _log_rebuild(self._drop_packed_mxfp8)
+            self._pk8 = ops.pack_conv_weight_mxfp8(self.weight, self.bias)
+            self._pk8_key = k
+        return self._pk8
+
+    def _drop_packed_mxfp8(self) -> None:
+        self._pk8, self._pk8_key = None, None
+        bump_cache_epoch()
 
     def packed(self) -> ops.PackedWeight:
         # logical Cout widened to a multiple of 8 (zero rows): 3/4-channel heads write 16-byte NHWC rows
@@ -153,8 +170,9 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
         p = self.padding[0] if pad is None else pad
         if out_dtype == ops.OUT_STREAM and self.out_inner16 and ops.precise():
             out_dtype = ops.OUT_BF16
+        fp8_pack = self.packed_mxfp8 if (self.fp8 and gn is not None and bias_override is None) else None
         return ops.conv2d(x, pw, stride=stride or self.stride[0], pad=p, upsample=upsample, act=act, residual=residual,
-                          gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn)
+                          gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack)
 
     def nhwc_multi(self, xs, *, pad=None, upsample=False, act=ops.ACT_NONE, residuals=None, stride=None, gn_groups=0,
                    out_dtype=ops.OUT_STREAM, out_split=1, gn=None):

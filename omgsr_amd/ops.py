@@ -571,6 +571,32 @@ def _fill_mxfp8(a: IgemmArgs, codes_ptr: int, scales_ptr: int, pw: PackedWeight)
     a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
 
 
+def pack_conv_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> PackedWeight:
+    """[Cout, Cin, 3, 3] bf16 -> the weight of omgsr_conv_mxfp8 (include/omgsr_hip.h): one MXFP8 block per 32 consecutive input channels of
+    one (cout, ky, kx), quantised on the device by quantize_mxfp8 (rows = (cout, tap), K = Cin), then laid out slice-major:
+    `w_cm` codes uint8 [Cin/64][9][Cout_pad][64], `w_scale` uint8 [Cin/64][Cout_pad][2][16] (byte t < 9 = tap t). Rows are padded with zeros
+    to a multiple of 128; `w` is the codes tensor too (the row-major packing does not exist in this form)."""
+    if _PRECISE or _ACT != torch.bfloat16:
+        raise ValueError("an fp8 (MXFP8) layer needs the bf16 compute type (the fp8 tier); the accurate tier and fp16 have none")
+    dev = device or weight.device
+    cout, cin, R, S = weight.shape
+    if (R, S) != (3, 3) or cin % 128:
+        raise ValueError(f"an fp8 (MXFP8) conv needs a 3x3 kernel and in_channels % 128 == 0, got {tuple(weight.shape)}")
+    cout8 = _round_up(cout, 8)
+    cout_pad = _round_up(cout8, 128)
+    w = torch.zeros((cout_pad, 9, cin), device=dev, dtype=torch.bfloat16)
+    w[:cout] = weight.detach().to(device=dev, dtype=torch.bfloat16).permute(0, 2, 3, 1).reshape(cout, 9, cin)
+    q = quantize_mxfp8(w)
+    codes = q.codes.view(cout_pad, 9, cin // 64, 64).permute(2, 1, 0, 3).contiguous()                 # [chunk][tap][cout][64]
+    sc = torch.zeros((cin // 64, cout_pad, 2, 16), device=dev, dtype=torch.uint8)
+    sc[..., :9] = q.scales.view(cout_pad, 9, cin // 64, 2).permute(2, 0, 3, 1)                          # [chunk][cout][block][tap]
+    b = None
+    if bias is not None:
+        b = torch.zeros(cout8, device=dev, dtype=torch.float32)
+        b[:cout] = bias.detach().to(device=dev, dtype=torch.float32)
+    return PackedWeight(codes.view(cin // 64 * 9 * cout_pad, 64), b, cout8, cin, 3, 3, w_cm=codes, w_scale=sc)
+
+
 # --------------------------------------------------------------------------------------------
 # K1-K3, K5, K6: implicit-GEMM conv / linear / bmm
 
@@ -698,7 +724,9 @@ class GnSpec:
         return self._table
 
     def apply(self, x: torch.Tensor, split: int = 1) -> torch.Tensor:
-        """The separate pass: stream tensor -> normalised operand in the form the consumer reads."""
+        """The separate pass: stream tensor -> normalised operand in the form the consumer reads (split 5: an Mxfp8)."""
+        if split == 5:
+            return group_norm_apply_mxfp8(x, self.mean, self.rstd, self.gamma, self.beta, self.groups, self.act)
         if self.mean.shape[0] != x.shape[0]:
             return group_norm_apply_shared(x, self.mean, self.rstd, self.gamma, self.beta, self.groups, self.act, split=split)
         return group_norm_apply(x, self.mean, self.rstd, self.gamma, self.beta, self.groups, self.act, split=split)
@@ -723,18 +751,23 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: tuple[int
            upsample: bool = False, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
            gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM, alpha: float = 1.0,
            out: Optional[torch.Tensor] = None, gn_groups: int = 0, out_split: int = 1, sample_rows: int = 0,
-           gn: Optional["GnSpec"] = None) -> torch.Tensor:
+           gn: Optional["GnSpec"] = None, fp8_pack=None) -> torch.Tensor:
     """x [N,H,W,Cin] operand (or a stream tensor: cast / split here) -> [N,Ho,Wo,Cout]. pad = (top, bottom, left, right) on
     the (virtual) input. out_dtype: OUT_STREAM (a stream tensor: default), OUT_BF16 (a 16-bit operand for the next GEMM,
     `out_split` 2 = written as the two-term split) or OUT_F32. residual: a stream tensor of the output's shape.
     gn_groups > 0: the caller will GroupNorm the result with that many groups; when the kernel can, it emits the
     (sum, sum of squares) partials from its epilogue and group_norm_stats() skips its read pass over the tensor.
     gn: x is the stream tensor a GroupNorm (+ SiLU) reads and the conv consumes the normalised tensor (GnSpec): fused into the conv's
-    patch producer where the library can, the apply pass in front of the conv otherwise."""
+    patch producer where the library can, the apply pass in front of the conv otherwise.
+    fp8_pack (a layer marked by precision.set_fp8_conv; needs gn): a callable returning the layer's pack_conv_weight_mxfp8 form. Where
+    omgsr_conv_mxfp8_ok accepts the problem (a per-problem decision from one sample's geometry), the GroupNorm runs as the apply pass that
+    writes MXFP8 and mxfp8_conv_kernel runs the conv; otherwise the call takes the 16-bit path below exactly as without it."""
     a = IgemmArgs()
     if gn is not None and not _gn_candidate(x, pw):
         x, gn = gn.apply(x, pw.split), None
     x, out = _conv_args(a, x, pw, stride, pad, upsample, act, residual, gate, out_dtype, alpha, out, out_split, sample_rows)
+    if fp8_pack is not None and gn is not None and out_split == 1 and _lib.load().omgsr_conv_mxfp8_ok(C.byref(a)):
+        return _conv2d_mxfp8(a, gn.apply(x, 5), fp8_pack(), out, gn_groups)
     if out_split == 4 and not _lib.load().omgsr_igemm_out_mx6_ok(C.byref(a)):
         # the fp6 operand form comes out of the halo-tile kernel's dedicated instantiations only: anything else writes a stream tensor and the
         # cast kernel makes the operand (one more pass over the tensor; small maps and GEMM-shaped problems)
@@ -754,6 +787,43 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: tuple[int
     if partial is not None:
         out._omgsr_gn = (partial, gn_groups, out.data_ptr(), out._version)      # consumed by group_norm_stats(out)
     return out
+
+
+def _conv2d_mxfp8(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight, out: torch.Tensor, gn_groups: int) -> torch.Tensor:
+    """Launch omgsr_conv_mxfp8 on an argument block filled for the 16-bit form of the same problem (geometry, epilogue, output)."""
+    if xq.codes.shape[-1] != pw8.cin or a.Cout != pw8.cout:
+        raise ValueError(f"conv2d_mxfp8: operand K {xq.codes.shape[-1]} / Cout {a.Cout} do not match the packed weight ({pw8.cin}, {pw8.cout})")
+    a.in_, a.in_scale = xq.codes.data_ptr(), xq.scales.data_ptr()
+    a.weight, a.weight_cm, a.w_scale, a.weight_ph = pw8.w_cm.data_ptr(), pw8.w_cm.data_ptr(), pw8.w_scale.data_ptr(), None
+    a.Cout_pad, a.K_pad = pw8.w_cm.shape[2], 9 * pw8.cin
+    a.bias = _ptr(pw8.bias) if a.bias is None else a.bias
+    partial = _conv_gn(a, gn_groups, 1, out.device)
+    check(_lib.load().omgsr_conv_mxfp8(C.byref(a), _stream()), "omgsr_conv_mxfp8")
+    if partial is not None:
+        out._omgsr_gn = (partial, gn_groups, out.data_ptr(), out._version)
+    return out
+
+
+def conv2d_mxfp8(xq: "Mxfp8", pw8: PackedWeight, *, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
+                 gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM, gn_groups: int = 0, sample_rows: int = 0) -> torch.Tensor:
+    """3x3 stride-1 pad-1 conv of an MXFP8 operand xq [N,H,W,Cin] (quantize_mxfp8 / group_norm_apply split 5) with a pack_conv_weight_mxfp8
+    weight -> [N,H,W,Cout8]. No other kernel stands behind it: a problem omgsr_conv_mxfp8_ok does not accept raises (OMGSR_E_SHAPE)."""
+    if not isinstance(xq, Mxfp8) or not pw8.fp8 or pw8.w_cm is None:
+        raise ValueError("conv2d_mxfp8: an Mxfp8 operand and a pack_conv_weight_mxfp8 weight")
+    N, H, W, Cin = xq.codes.shape
+    a = IgemmArgs()
+    out = _out_tensor((N, H, W), pw8.cout, out_dtype, 1, xq.codes.device)
+    if residual is not None and tuple(residual.shape) != (N, H, W, pw8.cout):
+        raise ValueError(f"residual shape {tuple(residual.shape)} != output {(N, H, W, pw8.cout)}")
+    a.gate = _ptr(gate)
+    _fill_out(a, out, 1, residual, pw8.cout)
+    a.N, a.H, a.W, a.Cin, a.Cout = N, H, W, Cin, pw8.cout
+    a.Cout_pad, a.K_pad = pw8.w_cm.shape[2], 9 * pw8.cin
+    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 3, 3, 1, 1, 1, 0
+    a.Ho, a.Wo, a.act, a.out_layout = H, W, act, LAYOUT_NHWC
+    a.batch, a.alpha, a.sample_rows = 1, 1.0, sample_rows or H * W
+    a.overflow_flag = None
+    return _conv2d_mxfp8(a, xq, pw8, out, gn_groups)
 
 
 def conv2d_multi(xs, pw: PackedWeight, *, stride: int = 1, pad: tuple[int, int, int, int] | int = 1, upsample: bool = False,
@@ -1207,7 +1277,12 @@ def group_norm_apply(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, ga
                      beta: Optional[torch.Tensor], groups: int, act: int = ACT_NONE, inplace: bool = False, split: int = 1,
                      also_cast: int = 0):
     """Stream tensor -> normalised (+SiLU) MFMA operand [..., split*C]. also_cast 1 | 2 | 3: additionally returns x itself as a
-    plain / two-term split / mixed-precision operand (the input of a ResnetBlock's 1x1 shortcut conv), written by the same pass."""
+    plain / two-term split / mixed-precision operand (the input of a ResnetBlock's 1x1 shortcut conv), written by the same pass.
+    split 5: the result as an Mxfp8 (group_norm_apply_mxfp8; no also_cast / inplace)."""
+    if split == 5:
+        if also_cast or inplace:
+            raise ValueError("group_norm_apply: split 5 (MXFP8) has no second output and cannot run in place")
+        return group_norm_apply_mxfp8(x, mean, rstd, gamma, beta, groups, act)
     xel = _el(x, "x")
     N, Cc = x.shape[0], x.shape[-1]
     HW = x.numel() // (N * Cc)
@@ -1220,6 +1295,22 @@ def group_norm_apply(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, ga
                                             _ovf(x.device) if fused else None, _stream()),
           "omgsr_groupnorm_apply")
     return (y, y2) if also_cast else y
+
+
+def group_norm_apply_mxfp8(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE) -> "Mxfp8":
+    """Stream tensor x [rows, ..., C] (bf16 or fp32, read only) -> act(GroupNorm(x)) as an Mxfp8 [rows, ..., C]: the fp32 result of the apply
+    arithmetic quantised by quantize_mxfp8's rule in the same pass (omgsr_groupnorm_apply_mxfp8). mean / rstd [N, G]: row r uses the
+    statistics of image r % N. C % 128 == 0, bf16 compute type."""
+    xel = _el(x, "x")
+    rows, Cc = x.shape[0], x.shape[-1]
+    HW = x.numel() // (rows * Cc)
+    if Cc % 128:
+        raise ValueError(f"group_norm_apply_mxfp8: C = {Cc} is not a multiple of 128")
+    codes = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+    scales = torch.empty((*x.shape[:-1], Cc // 32), device=x.device, dtype=torch.uint8)
+    check(_lib.load().omgsr_groupnorm_apply_mxfp8(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
+                                                  _ptr(beta), rows, HW, Cc, groups, act, mean.shape[0], xel, _stream()), "omgsr_groupnorm_apply_mxfp8")
+    return Mxfp8(codes, scales)
 
 
 def group_norm(x: torch.Tensor, gamma, beta, groups: int, eps: float, act: int = ACT_NONE, split: int = 1, also_cast: int = 0):

@@ -47,14 +47,21 @@ class OMGSR_F_Infer(torch.nn.Module):
         # weight_dtype=torch.float8_e4m3fn: the fp8 tier - the bf16 tier with the DiT's token linears as MXFP8 x MXFP8 GEMMs (precision.FLUX_FP8;
         # precision_policy={"flux": {"fp8": [patterns]}} narrows the list). Modules are held and LoRA-merged in bf16, their fp8 forms packed lazily.
         # precision_policy={"flux": {"fp8_attention": True | [block patterns]}} (fp8 tier only, opt-in) also runs those blocks' joint attention
-        # on MXFP8 q / k / V^T (precision.set_fp8_attention).
+        # on MXFP8 q / k / V^T (precision.set_fp8_attention). precision_policy={"vae": {"fp8": True | [layer patterns]}} (fp8 tier only, opt-in)
+        # runs those resnet convs of the VAE as MXFP8 convolutions where the kernel serves them (precision.set_fp8_conv); the tiled VAE is not served.
         fp8 = weight_dtype == torch.float8_e4m3fn
-        if fp8 and precision_policy is not None and not (isinstance(precision_policy, dict) and set(precision_policy) <= {"flux"} and
-                                                         set(precision_policy.get("flux", {})) <= {"fp8", "fp8_attention"}):
-            raise ValueError("the fp8 tier's precision_policy is {'flux': {'fp8': [patterns], 'fp8_attention': True | [block patterns]}}")
+        if fp8 and precision_policy is not None and not (isinstance(precision_policy, dict) and set(precision_policy) <= {"flux", "vae"} and
+                                                         isinstance(precision_policy.get("flux", {}), dict) and
+                                                         isinstance(precision_policy.get("vae", {}), dict) and
+                                                         set(precision_policy.get("flux", {})) <= {"fp8", "fp8_attention"} and
+                                                         set(precision_policy.get("vae", {})) <= {"fp8"}):
+            raise ValueError("the fp8 tier's precision_policy is {'flux': {'fp8': [patterns], 'fp8_attention': True | [block patterns]}, "
+                             "'vae': {'fp8': True | [layer patterns]}}")
         if not fp8:
-            from ..precision import refuse_fp8_attention
+            from ..precision import refuse_fp8_attention, refuse_fp8_conv
             refuse_fp8_attention(precision_policy, f"the {weight_dtype} tier")
+            refuse_fp8_conv(precision_policy, f"the {weight_dtype} tier")
+        fp8_vae = (precision_policy or {}).get("vae", {}).get("fp8") if fp8 else None
         fp8_patterns = (precision_policy or {}).get("flux", {}).get("fp8") if fp8 else None
         fp8_attention = (precision_policy or {}).get("flux", {}).get("fp8_attention") if fp8 else None
         weight_dtype = torch.bfloat16 if fp8 else weight_dtype
@@ -92,6 +99,12 @@ class OMGSR_F_Infer(torch.nn.Module):
             set_fp8_attention(self.flux_transformer, fp8_attention)
         else:
             clear_fp8_attention(self.flux_transformer)
+        from ..precision import clear_fp8_conv, set_fp8_conv
+        if fp8 and fp8_vae not in (None, False):
+            set_fp8_conv(self.vae, fp8_vae)
+        else:
+            clear_fp8_conv(self.vae)
+        self.fp8_vae = bool(fp8 and fp8_vae not in (None, False))
         if weight_dtype == torch.float32:
             from ..precision import resolve
             resolve(precision_policy, vae=self.vae, flux=self.flux_transformer)
@@ -116,6 +129,9 @@ class OMGSR_F_Infer(torch.nn.Module):
 
     def _init_tiled_vae(self, encoder_tile_size=256, decoder_tile_size=256, fast_decoder=False, fast_encoder=False,
                         color_fix=False, vae_to_gpu=True):
+        if getattr(self, "fp8_vae", False):
+            raise ValueError("the tiled VAE is not served by the fp8 VAE convolutions (precision_policy {'vae': {'fp8': ...}}): its launch groups "
+                             "run the bf16 kernels only - build the pipeline without that key to tile")
         from .vaehook import VAEHook
         self.vae.encoder._tile_hook = VAEHook(self.vae.encoder, encoder_tile_size, is_decoder=False, fast_decoder=fast_decoder,
                                               fast_encoder=fast_encoder, color_fix=color_fix, to_gpu=vae_to_gpu)

@@ -312,6 +312,72 @@ def fp8_layers(model: nn.Module) -> list:
     return [name for name, m in model.named_modules() if isinstance(m, Linear) and m.fp8]
 
 
+# The VAE's 3x3 convolutions in the fp8 tier (opt-in: precision_policy={"vae": {"fp8": True | [patterns]}}): a marked conv runs as an
+# MXFP8 x MXFP8 convolution (mxfp8_conv_kernel) behind a GroupNorm + SiLU apply pass that writes MXFP8, wherever the library serves the problem
+# (omgsr_conv_mxfp8_ok: the halo-tile kernel's spatial form, Cin % 128 == 0); every other problem of a marked layer takes the bf16 path as
+# before. VAE_FP8_ELIGIBLE is the hard limit - the resnet conv1 / conv2 of encoder, decoder and both mid blocks, the only convs that read a
+# GroupNorm + SiLU output; conv_in / conv_out, the quant convs, the samplers and conv_shortcut never move. VAE_FP8 is what `True` marks: the
+# DECODER's 28 layers. Every eligible shape is faster in MXFP8 (1.19-1.70x, profiles/fp8_vae.json), but with all 48 layers the full-depth
+# OMGSR-F 256 -> 1024 output falls to 29.0-30.0 dB against the accurate tier (target >= 30 dB on three draws; the fp8 tier alone: 32.8-34.4);
+# decoder only holds 30.4-31.5 dB, encoder only 30.7-31.9 (DESIGN.md 3.4 has the per-group table). Encoder layers still move when named.
+VAE_FP8_ELIGIBLE = [r"^(encoder|decoder)\.(down_blocks\.\d+|up_blocks\.\d+|mid_block)\.resnets\.\d+\.conv[12]$"]
+VAE_FP8 = [r"^decoder\.(up_blocks\.\d+|mid_block)\.resnets\.\d+\.conv[12]$"]
+
+
+def _fp8_conv_candidates(model: nn.Module):
+    elig = [re.compile(p) for p in VAE_FP8_ELIGIBLE]
+    return [(name, m) for name, m in model.named_modules() if isinstance(m, Conv2d) and any(r.search(name) for r in elig)]
+
+
+def set_fp8_conv(model: nn.Module, patterns) -> int:
+    """Mark the convs of an AutoencoderKL whose names match `patterns` (a list of regular expressions, re.search; True = VAE_FP8) and
+    VAE_FP8_ELIGIBLE as fp8 (nn.Conv2d.fp8); every other conv is unmarked. ValueError for anything else than True or a list of strings, for a
+    pattern that names no eligible layer (True included, should VAE_FP8 be empty), and outside the bf16 compute type. Returns how many
+    layers are marked."""
+    from . import ops
+    if ops.precise() or ops.act_dtype() != torch.bfloat16:
+        raise ValueError("fp8 convolutions need the bf16 compute type (the fp8 tier); the accurate tier and fp16 have none")
+    if patterns is True:
+        if not VAE_FP8:
+            raise ValueError("vae fp8: no layer is enabled by default (precision.VAE_FP8 is empty): name the layers with a pattern list")
+        patterns = list(VAE_FP8)
+    elif not isinstance(patterns, (list, tuple)) or not patterns or not all(isinstance(p, str) for p in patterns):
+        raise ValueError(f"vae fp8 is True or a list of layer-name patterns, got {patterns!r}")
+    regs = [re.compile(p) for p in patterns]
+    cand = _fp8_conv_candidates(model)
+    dead = [r.pattern for r in regs if not any(r.search(name) for name, _ in cand)]
+    if dead:            # a typo would otherwise run the plain fp8 tier without a word
+        raise ValueError(f"vae fp8 patterns that name no eligible layer (the resnet conv1 / conv2 of encoder / decoder): {dead}")
+    _touch()
+    want = {name for name, _ in cand if any(r.search(name) for r in regs)}
+    n = 0
+    for name, m in model.named_modules():
+        if isinstance(m, Conv2d):
+            m.fp8 = name in want
+            n += m.fp8
+    return n
+
+
+def clear_fp8_conv(model: nn.Module) -> None:
+    """Unmark every fp8 conv of `model` (a pipeline of another tier, or the fp8 tier without the key, built on marked modules)."""
+    if any(isinstance(m, Conv2d) and m.fp8 for m in model.modules()):
+        _touch()
+        for m in model.modules():
+            if isinstance(m, Conv2d):
+                m.fp8 = False
+
+
+def fp8_conv_layers(model: nn.Module) -> list:
+    """Names of the fp8 convs of `model`."""
+    return [name for name, m in model.named_modules() if isinstance(m, Conv2d) and m.fp8]
+
+
+def refuse_fp8_conv(policy, where: str) -> None:
+    """ValueError when a precision_policy asks for fp8 VAE convolutions outside the fp8 tier."""
+    if isinstance(policy, dict) and isinstance(policy.get("vae"), dict) and "fp8" in policy["vae"]:
+        raise ValueError(f"vae fp8 belongs to OMGSR-F's fp8 tier (weight_dtype=torch.float8_e4m3fn), not to {where}")
+
+
 def set_mx(model: nn.Module, patterns: Iterable[str]) -> int:
     """Move the both-sides split of the matching 3x3 stride-1 (halo-tile kernel) and 1x1 (MX GEMM kernel) convolutions (Cin % 64 == 0,
     >= 96 output channels) to the mixed-precision form (op_split 3); layers that do not qualify keep what they had. OMGSR_MX=0

@@ -1,0 +1,205 @@
+"""The fp8 tier's opt-in VAE convolutions (precision_policy {"vae": {"fp8": ...}}) against the bf16 VAE, in one process (bench.py never runs them):
+
+  * layers: every eligible layer shape of the FLUX VAE at 1024^2, batch 8 - GroupNorm + SiLU + 3x3 conv as the bf16 path runs it (the halo
+    kernel with the norm fused into its patch producer, or the apply pass + the halo kernel) against the apply-to-MXFP8 pass + mxfp8_conv_kernel;
+    HIP events, alternated rounds. A shape belongs in precision.VAE_FP8 only if the fp8 arm wins in every round;
+  * step: VAE encode, VAE decode and the whole OMGSR-F 256 -> 1024 batch-8 step (bench.py's f1024 workload) in the fp8 tier with and without
+    the key, same process, alternated rounds;
+  * quality (--quality): full depth, OMGSR-F 256 -> 1024, batch 1, seeded draws, the fp8 tier with and without the key against the accurate tier.
+
+    python tools/bench_fp8_vae.py [--rounds 3] [--no-step] [--quality] [--out profiles/fp8_vae.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+# (map side, Cin, Cout, layers of that shape in encoder + decoder) of the FLUX VAE's resnet conv1 / conv2 at 1024^2
+SHAPES = [(1024, 128, 128, 4 + 5), (1024, 256, 128, 1), (512, 128, 256, 1), (512, 256, 256, 3 + 5), (512, 512, 256, 1),
+          (256, 256, 512, 1), (256, 512, 512, 3 + 6), (128, 512, 512, 8 + 10)]
+
+
+def _events_ms(fn, iters: int) -> float:
+    import torch
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def layer_table(dev, batch: int, rounds: int) -> list:
+    import torch
+    from omgsr_amd import ops
+    rows = []
+    for side, cin, cout, count in SHAPES:
+        g = torch.Generator(device=dev).manual_seed(side + cin + cout)
+        x = torch.randn(batch, side, side, cin, generator=g, device=dev).to(torch.bfloat16)
+        w = (torch.randn(cout, cin, 3, 3, generator=g, device=dev) / (3.0 * cin ** 0.5)).to(torch.bfloat16)
+        b = torch.zeros(cout, device=dev)
+        p16 = ops.pack_conv_weight(w, b)
+        p8 = ops.pack_conv_weight_mxfp8(w, b)
+        gamma, beta = torch.ones(cin, device=dev), torch.zeros(cin, device=dev)
+        mean, rstd, _ = ops.group_norm_stats(x, 32, 1e-6)
+        spec = lambda: ops.GnSpec(mean, rstd, gamma, beta, 32, ops.ACT_SILU)      # noqa: E731  (a fresh spec per call: its table is built per call)
+        arms = {"bf16": lambda: ops.conv2d(x, p16, gn=spec(), gn_groups=32),
+                "fp8": lambda: ops.conv2d(x, p16, gn=spec(), gn_groups=32, fp8_pack=lambda: p8),
+                "fp8_apply_only": lambda: spec().apply(x, 5)}
+        for fn in arms.values():
+            for _ in range(2):
+                fn()
+        iters = 10 if side >= 512 else 30
+        t = {k: [] for k in arms}
+        for r in range(rounds):
+            for k in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+                t[k].append(_events_ms(arms[k], iters))
+        fl = 2.0 * batch * side * side * 9 * cin * cout
+        row = dict(side=side, cin=cin, cout=cout, batch=batch, layers=count,
+                   bf16_ms=[round(v, 4) for v in t["bf16"]], fp8_ms=[round(v, 4) for v in t["fp8"]], fp8_apply_ms=[round(v, 4) for v in t["fp8_apply_only"]],
+                   speedup_median=round(statistics.median(t["bf16"]) / statistics.median(t["fp8"]), 3),
+                   fp8_conv_tflops=round(fl / (statistics.median(t["fp8"]) - statistics.median(t["fp8_apply_only"])) / 1e9, 1),
+                   bf16_tflops=round(fl / statistics.median(t["bf16"]) / 1e9, 1),
+                   fp8_faster_in_every_round=all(a > c for a, c in zip(t["bf16"], t["fp8"])))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del x, w, p16, p8
+        torch.cuda.empty_cache()
+    return rows
+
+
+def step_rounds(dev, rounds: int, steps: int) -> dict:
+    import torch
+    import bench
+    from omgsr_amd import ops
+    from omgsr_amd.precision import FLUX_FP8, clear_fp8_conv, fp8_conv_layers, set_fp8_conv, set_fp8_linear
+    family, side, B, tile, overlap, _ = bench.WORKLOADS["f1024"]
+    pipe, _ = bench.build_f(dev, 0, 1, torch.bfloat16)
+    set_fp8_linear(pipe.flux_transformer, FLUX_FP8)
+    inp = bench.make_inputs(family, side, B, tile, 0, dev, torch.bfloat16)
+    pipe.vae.posterior_noise = inp["eps"].to(dev)
+    step = bench.make_step(pipe, family, inp, tile, overlap)
+    lq = ops.nchw_to_nhwc(inp["lq"].to(dev, torch.bfloat16).contiguous(), 8)
+    z = torch.randn(B, side // 8, side // 8, 16, device=dev).to(torch.bfloat16)
+    parts = {"step": step, "encode": lambda: pipe.vae.encode_moments_nhwc(lq), "decode": lambda: pipe.vae.decode_nhwc(z)}
+    times = {arm: {k: [] for k in parts} for arm in ("fp8_tier", "fp8_tier_vae_fp8")}
+    marked = 0
+    with torch.no_grad():
+        for r in range(rounds):
+            for arm in (list(times) if r % 2 == 0 else list(times)[::-1]):
+                if arm == "fp8_tier":
+                    clear_fp8_conv(pipe.vae)
+                else:
+                    marked = set_fp8_conv(pipe.vae, True)
+                for k, fn in parts.items():
+                    fn(); fn()                      # warm: (re-)packs
+                    torch.cuda.synchronize()
+                    for _ in range(steps):
+                        t0 = time.perf_counter()
+                        fn()
+                        torch.cuda.synchronize()
+                        times[arm][k].append(time.perf_counter() - t0)
+                print(f"round {r} {arm}: " + ", ".join(f"{k} {statistics.median(v[-steps:]) * 1e3:.1f} ms" for k, v in times[arm].items()), flush=True)
+        names = fp8_conv_layers(pipe.vae)
+        clear_fp8_conv(pipe.vae)
+    out = {"marked_layers": marked or len(names)}
+    for arm, d in times.items():
+        out[arm] = {k: dict(median_ms=round(statistics.median(v) * 1e3, 2), min_ms=round(min(v) * 1e3, 2), max_ms=round(max(v) * 1e3, 2)) for k, v in d.items()}
+    out["shape"] = dict(workload="f1024", side=side, batch=B, tile=tile, overlap=overlap)
+    return out
+
+
+# the per-group table of the quality leg: the fp8 tier alone, the whole default list, then encoder / decoder / mid blocks and resolution levels
+GROUPS = {"fp8_tier": None, "vae_fp8_true": True, "encoder": [r"^encoder\."], "decoder": [r"^decoder\."], "mid_blocks": [r"mid_block"],
+          "decoder_128_256px": [r"^decoder\.up_blocks\.[01]\."], "decoder_512px": [r"^decoder\.up_blocks\.2\."], "decoder_1024px": [r"^decoder\.up_blocks\.3\."],
+          "encoder_1024px": [r"^encoder\.down_blocks\.0\."], "encoder_512px_and_below": [r"^encoder\.down_blocks\.[123]\."]}
+
+
+def quality(dev, draws: int) -> list:
+    """Full depth, OMGSR-F 256 -> 1024, batch 1 (tests/test_fp8_gpu.py's full-depth case, per draw): PSNR / rel-L2 against the accurate tier."""
+    import torch
+    from omgsr_amd import ops
+    from omgsr_amd.diffusers_api import AutoencoderKL, FLUX_VAE_CONFIG, FluxTransformer2DModel
+    from omgsr_amd.pipelines.omgsr_f import OMGSR_F_Infer, prepare_latent_image_ids
+    from omgsr_amd.testing import psnr, rel_l2, seeded_init_, seeded_init_device_, synthetic_lq
+    rows = []
+    for draw in range(draws):
+        ops.set_compute_dtype(torch.float32)
+        with torch.device("meta"):
+            pf = FluxTransformer2DModel()
+        pf = pf.to_empty(device=dev)
+        seeded_init_device_(pf, 404 + 31 * draw)
+        pf.round_timestep_to_weight_dtype = False
+        vae_sd = seeded_init_(AutoencoderKL(**FLUX_VAE_CONFIG), 303 + 31 * draw, rounded=False).state_dict()
+        g = torch.Generator().manual_seed(4321 + draw)
+        x = synthetic_lq(1, 1024, 1024, seed=1234 + draw).to(dev)
+        eps = torch.randn(1, 16, 128, 128, generator=torch.Generator().manual_seed(99 + draw)).to(dev)
+        pe, pooled = torch.randn(1, 512, 4096, generator=g).to(dev), torch.randn(1, 768, generator=g).to(dev)
+        tids, iids = torch.zeros(512, 3, device=dev), prepare_latent_image_ids(64, 64, dev, torch.float32)
+
+        def run(wd, policy=None):
+            pv = AutoencoderKL(**FLUX_VAE_CONFIG)
+            pv.load_state_dict(vae_sd)
+            pipe = OMGSR_F_Infer(None, None, dev, wd, 244, 1.0, vae=pv, flux_transformer=pf, precision_policy=policy)
+            pipe.vae.posterior_noise = eps
+            cd = torch.float32 if wd == torch.float32 else torch.bfloat16
+            with torch.no_grad():
+                return pipe(x.to(cd), pe.to(cd), pooled.to(cd), tids.to(cd), iids.to(cd), 128, 64)[0].float()
+
+        ref = run(torch.float32)
+        row = dict(draw=draw)
+        for name, pol in GROUPS.items():
+            y = run(torch.float8_e4m3fn, None if pol is None else {"vae": {"fp8": pol}})
+            row[name] = dict(rel_l2=rel_l2(y, ref), psnr_db=round(psnr(y, ref), 2))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del pf
+        torch.cuda.empty_cache()
+    ops.set_compute_dtype(torch.bfloat16)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed calls per arm per round")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--no-layers", action="store_true")
+    ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--quality", action="store_true", help="also the full-depth quality draws (minutes)")
+    ap.add_argument("--draws", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp8_vae.json"))
+    args = ap.parse_args()
+    import torch
+    from omgsr_amd import _lib, ops
+    dev = torch.device("cuda", 0)
+    _lib.check(_lib.load().omgsr_check_device(), "omgsr_check_device")
+    ops.set_compute_dtype(torch.bfloat16)
+    rec = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__)
+    if os.path.isfile(args.out):                    # sections measured by an earlier call stay
+        with open(args.out) as f:
+            rec = {**json.load(f), **rec}
+    if not args.no_layers:
+        rec["layers"] = layer_table(dev, args.batch, args.rounds)
+    if not args.no_step:
+        rec["f1024_b8"] = step_rounds(dev, args.rounds, args.steps)
+        print(json.dumps(rec["f1024_b8"]), flush=True)
+    if args.quality:
+        rec["full_depth_quality"] = quality(dev, args.draws)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(f"wrote {args.out}")
+
+
+if __name__ == "__main__":
+    main()
