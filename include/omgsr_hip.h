@@ -217,6 +217,19 @@ int omgsr_igemm(const omgsr_igemm_args* a, void* stream);
  * GroupNorm-producer / upsample / out_lo_off / out_mx fields. omgsr_conv_mxfp8 returns OMGSR_E_SHAPE for anything else (never another kernel). */
 int32_t omgsr_conv_mxfp8_ok(const omgsr_igemm_args* a);
 int omgsr_conv_mxfp8(const omgsr_igemm_args* a, void* stream);
+/* Additive under ABI v22 (no struct changed): the problems of ONE tiled-VAE layer (tile-shape groups: the same weight, w_scale, Cin, Cout,
+ * bias, act, gate, alpha, output and residual element kinds; their own N / H / W and tensors) through mxfp8_conv_multi_kernel, at most 8 per
+ * launch (a larger `count` runs as successive launches of at most 8; a group of one launches mxfp8_conv_kernel).
+ * omgsr_conv_mxfp8_multi_ok: 1 when every problem passes omgsr_conv_mxfp8_ok's kernel-side rules and the spatial form's geometry rules
+ * (Wo >= 16, roundup32(Wo) * 3 <= Wo * 4 - no FLAT escape: that form is not built in MXFP8), the problems agree in everything a launch shares,
+ * and the SUM of their spatial-form tile counts reaches the dispatcher's 192 (in batch-invariant mode every problem is judged alone, from one
+ * sample's rows, as omgsr_conv_mxfp8_ok does). One answer per layer: otherwise the whole layer belongs on the 16-bit path.
+ * omgsr_conv_mxfp8_multi returns OMGSR_E_SHAPE for anything _multi_ok refuses (never another kernel). gn_partial of a problem: the slot layout
+ * and values its own omgsr_conv_mxfp8 call produces (2 x its spatial tiles per image; entries as omgsr_igemm_gn_entries answers once
+ * group_tiles holds the group's total N x ceil(Wo / 32) x ceil(Ho / 8) x ceil(Cout / 128) summed over the problems - 0 in batch-invariant
+ * mode; the entry points put it there themselves, whatever the field held). */
+int32_t omgsr_conv_mxfp8_multi_ok(const omgsr_igemm_args* args, int32_t count);
+int omgsr_conv_mxfp8_multi(const omgsr_igemm_args* args, int32_t count, void* stream);
 /* The problems of ONE layer that differ only in tensors and spatial extents (the tiled VAE runs every layer once per tile-shape group:
  * corner / edge / interior tiles are separate dense tensors; infer/vaehook.py:537-829 walks them one tile at a time). Call
  * omgsr_igemm_multi_plan first: it writes `group_tiles` into every problem, so that omgsr_igemm_gn_slots / _gn_entries /
@@ -314,6 +327,12 @@ int omgsr_groupnorm_apply_multi(const omgsr_gn_apply_group* groups, int32_t ngro
 int omgsr_groupnorm_apply_mxfp8(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma,
                                 const float* beta, int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
                                 int32_t x_el, void* stream);
+/* Additive under ABI v22: omgsr_groupnorm_apply_mxfp8 over up to OMGSR_GN_MAX_GROUPS tensors of one channel count and element kind in ONE
+ * launch (gn_apply_mxfp8_multi_kernel; the groups of omgsr_groupnorm_apply_multi with y = codes, y2 = scales, both set). Row r of every tensor
+ * uses the statistics of image r % stat_rows; the bytes written equal those of one omgsr_groupnorm_apply_mxfp8 call per tensor. */
+int omgsr_groupnorm_apply_mxfp8_multi(const omgsr_gn_apply_group* groups, int32_t ngroups, const float* mean, const float* rstd,
+                                      const float* gamma, const float* beta, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                      int32_t x_el, void* stream);
 int omgsr_groupnorm_finalize2(const float* partial_a, int32_t nslot_a, int32_t Ca, const float* partial_b, int32_t nslot_b, int32_t Cb,
                               float* mean, float* rstd, float* var_out, int32_t N, int32_t G, double count, float eps, void* stream);
 int omgsr_groupnorm_apply2(const void* xa, const void* xb, int32_t Ca, void* y, const float* mean, const float* rstd, const float* gamma,
@@ -518,7 +537,7 @@ int omgsr_timing_reset(void);
  * OMGSR_EL_MX operand), 10 / 11 igemm_halo_kernel / igemm_halo_multi_kernel with the GroupNorm apply fused into the patch producer, 12 the halo
  * kernel's split-K (chunk ranges as one igemm_halo_multi_kernel launch + splitk_reduce_kernel), 13 / 14 / 15 the halo kernel with fp6
  * (OMGSR_EL_MX6) correction chunks: single, launch group, split-K, 16 / 17 the same in the phase-decomposed form: single, launch group,
- * 18 mxfp8_gemm_kernel (ABI v18).
+ * 18 mxfp8_gemm_kernel (ABI v18), 21 mxfp8_conv_kernel (ABI v22), 22 mxfp8_conv_multi_kernel (several problems of one layer in one launch).
  * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19), 20 vae_attn_kernel (ABI v20, D = 512). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;

@@ -1,4 +1,5 @@
-// MXFP8 x MXFP8 3x3 stride-1 pad-1 convolution (the fp8 tier's opt-in VAE convs; omgsr_conv_mxfp8, timing variant 21, kind 1).
+// MXFP8 x MXFP8 3x3 stride-1 pad-1 convolution (the fp8 tier's opt-in VAE convs; omgsr_conv_mxfp8, timing variant 21, kind 1; several
+// problems of one layer in one launch: omgsr_conv_mxfp8_multi, mxfp8_conv_multi_kernel, variant 22 - the same tile body after the lookup).
 //
 // mxfp8_conv_kernel runs the halo-tile schedule of igemm_halo_body.hip.h (8 x 32-pixel x 128-cout tile, patch LDS-DMA'd once per chunk and
 // read by all nine taps at shifted rows, 3-deep weight ring, one raw barrier and one counted vmcnt wait per K-step, XCD remap) on fp8 codes:
@@ -46,7 +47,8 @@ OMGSR_DEVINL u32x4_t gload16(const void* src) {
     return v;
 }
 
-__global__ __launch_bounds__(256, 2) void mxfp8_conv_kernel(const omgsr_igemm_args p, const IgemmGeo g) {
+// The tile body of both kernels below. `tile`: the problem's logical (XCD-remapped) tile index.
+OMGSR_DEVINL void mxfp8_conv_body(const omgsr_igemm_args& p, const IgemmGeo& g, const int tile) {
     using T = bf16_t;
     constexpr int WTN = 64, FM = 4, FN = 2, BNK = 128, TAPS = 9;
     constexpr int PW = MG::PW, PROWS = MG::PROWS, APIECES = MG::APIECES, APW = MG::APW, A_BYTES = MG::A_BYTES;
@@ -60,7 +62,6 @@ __global__ __launch_bounds__(256, 2) void mxfp8_conv_kernel(const omgsr_igemm_ar
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave >> 1, wn = wave & 1;
 
-    const int tile = xcd_remap((int)blockIdx.x, g.ntm * g.ntn);
     const int tn = tile % g.ntn, tm = tile / g.ntn;
     const int per_img = g.tiles_x * g.tiles_y;
     const int img = tm / per_img;
@@ -263,6 +264,22 @@ __global__ __launch_bounds__(256, 2) void mxfp8_conv_kernel(const omgsr_igemm_ar
     igemm_epilogue<T, WTN, FM, FN>(p, acc, epi, lane, mb, nv, n0 + wn * WTN, 0, gn_dst, 0, 1, 0);
 }
 
+__global__ __launch_bounds__(256, 2) void mxfp8_conv_kernel(const omgsr_igemm_args p, const IgemmGeo g) {
+    mxfp8_conv_body(p, g, xcd_remap((int)blockIdx.x, g.ntm * g.ntn));
+}
+
+// Several problems that share the weight, its scales, Cin / Cout and the epilogue options in ONE launch (the tile-shape groups of a tiled-VAE
+// layer; timing variant 22): HaloMulti as igemm_halo_multi_kernel reads it - the workgroup looks its problem up in the prefix table of
+// 8-aligned block ranges (wave-uniform: blockIdx and kernel arguments only), the filler blocks exit, and the body above runs unchanged.
+__global__ __launch_bounds__(256, 2) void mxfp8_conv_multi_kernel(const HaloMulti m) {
+    int s = 0;
+    while (s + 1 < m.count && (int)blockIdx.x >= m.start[s + 1]) ++s;
+    const int bid = (int)blockIdx.x - m.start[s];
+    const int ntiles = m.g[s].ntm * m.g[s].ntn;
+    if (bid >= ntiles) return;
+    mxfp8_conv_body(m.p[s], m.g[s], xcd_remap(bid, ntiles));
+}
+
 }  // namespace
 
 namespace omgsr {
@@ -290,6 +307,38 @@ int mxfp8_conv_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, con
     TimingScope ts(OMGSR_TK_IGEMM, flops, bytes, st, (long long)M, a.Cout, 9ll * a.Cin);
     if (ts.active) ts.rec.variant = 21;
     hipLaunchKernelGGL(mxfp8_conv_kernel, dim3(g.ntm * g.ntn), dim3(256), MXC_LDS_BYTES, st, a, g);
+    return (int)hipGetLastError();
+}
+
+// `count` problems (2 ... HALO_MULTI_MAX) that omgsr_conv_mxfp8_multi_ok accepted as one group, in one launch of mxfp8_conv_multi_kernel
+int mxfp8_conv_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, const int count, hipStream_t st, const double flops) {
+    if (count < 2 || count > HALO_MULTI_MAX) return OMGSR_E_BADARG;
+    HaloMulti m{};
+    m.count = count;
+    int at = 0;
+    double M = 0.0, bytes = (1.0 + 1.0 / 32.0) * (double)a[0].Cout_pad * a[0].K_pad;
+    for (int i = 0; i < count; ++i) {
+        m.p[i] = a[i];
+        m.g[i] = g0[i];
+        const bool narrow = halo_geo(a[i], m.g[i], false);
+        if (narrow || m.g[i].flat) return OMGSR_E_SHAPE;      // (omgsr_conv_mxfp8_multi_ok refused both: never reached)
+        m.start[i] = at;
+        at += (m.g[i].ntm * m.g[i].ntn + 7) & ~7;
+        const double Mi = (double)a[i].N * a[i].Ho * a[i].Wo;
+        M += Mi;
+        bytes += (1.0 + 1.0 / 32.0) * (double)a[i].N * a[i].H * a[i].W * a[i].Cin +
+                 Mi * a[i].Cout * ((a[i].out_dtype == OMGSR_OUT_F32 ? 4.0 : 2.0) + (a[i].residual ? (a[i].res_el == OMGSR_EL_F32 ? 4.0 : 2.0) : 0.0));
+    }
+    m.start[count] = at;
+    static bool attr_set = false;
+    if (!attr_set) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mxfp8_conv_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MXC_LDS_BYTES);
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    TimingScope ts(OMGSR_TK_IGEMM, flops, bytes, st, (long long)M, a[0].Cout, 9ll * a[0].Cin);
+    if (ts.active) ts.rec.variant = 22;
+    hipLaunchKernelGGL(mxfp8_conv_multi_kernel, dim3(at), dim3(256), MXC_LDS_BYTES, st, m);
     return (int)hipGetLastError();
 }
 }  // namespace omgsr

@@ -668,6 +668,7 @@ extern "C" int omgsr_igemm_multi(const omgsr_igemm_args* args, int32_t count, vo
 namespace omgsr {
 bool mxfp8_conv_shape_ok(const omgsr_igemm_args& a);
 int mxfp8_conv_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, double flops);
+int mxfp8_conv_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int count, hipStream_t st, double flops);
 }
 namespace {
 // Served: what mxfp8_conv_kernel runs AND the geometry for which this dispatcher hands the bf16 problem to the halo-tile kernel's spatial
@@ -696,6 +697,74 @@ extern "C" int omgsr_conv_mxfp8(const omgsr_igemm_args* ap, void* stream) {
     double flops, bytes;
     work_of(a, &flops, &bytes);
     return omgsr::mxfp8_conv_launch(a, geo_of(a), (hipStream_t)stream, flops);
+}
+
+// ---- additive under ABI v22: the tile-shape groups of one tiled-VAE layer through mxfp8_conv_multi_kernel -------------------------------
+namespace {
+constexpr int MXC_MULTI_MAX = 8;                // problems per launch (HALO_MULTI_MAX)
+// One answer for the layer. The group's total of spatial-form tiles stands in every member's `group_tiles` (> 0: the spatial form, so use_halo's
+// column rule has no FLAT escape and its tile-count policy sees the group); in batch-invariant mode group_tiles stays 0 and every member is
+// judged alone from one sample's rows, as omgsr_conv_mxfp8_ok judges it.
+bool conv_mxfp8_multi_ok(const omgsr_igemm_args* args, const int count) {
+    if (!args || count <= 0) return false;
+    int total = 0;
+    for (int i = 0; i < count; ++i) total += omgsr::igemm_halo_tiles_form(args[i], 0);
+    const omgsr_igemm_args& f = args[0];
+    for (int i = 0; i < count; ++i) {
+        omgsr_igemm_args a = args[i];
+        a.group_tiles = omgsr::g_batch_invariant ? 0 : total;
+        if (!conv_mxfp8_ok(a)) return false;
+        const int padded_w = ((a.Wo + 31) / 32) * 32;
+        if (a.Wo < 16 || padded_w * 3 > a.Wo * 4) return false;          // (whatever OMGSR_IGEMM_MODE says: the FLAT form does not exist here)
+        const bool same = a.weight_cm == f.weight_cm && a.w_scale == f.w_scale && a.Cin == f.Cin && a.Cout == f.Cout && a.Cout_pad == f.Cout_pad &&
+                          a.K_pad == f.K_pad && a.bias == f.bias && a.gate == f.gate && a.alpha == f.alpha && a.act == f.act && a.out_dtype == f.out_dtype &&
+                          a.out_ld == f.out_ld && a.res_el == f.res_el && (a.residual != nullptr) == (f.residual != nullptr) &&
+                          (a.gn_partial != nullptr) == (f.gn_partial != nullptr) && a.gn_groups == f.gn_groups && a.gn_entries == f.gn_entries &&
+                          a.overflow_flag == f.overflow_flag;
+        if (!same) return false;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int32_t omgsr_conv_mxfp8_multi_ok(const omgsr_igemm_args* args, int32_t count) { return conv_mxfp8_multi_ok(args, count) ? 1 : 0; }
+
+extern "C" int omgsr_conv_mxfp8_multi(const omgsr_igemm_args* args, int32_t count, void* stream) {
+    if (!args || count <= 0) return OMGSR_E_BADARG;
+    if (!conv_mxfp8_multi_ok(args, count)) return OMGSR_E_SHAPE;
+    int total = 0;
+    for (int i = 0; i < count; ++i) total += omgsr::igemm_halo_tiles_form(args[i], 0);
+    // a member as the launch sees it: the group's total in group_tiles (what its gn_partial layout was planned with), in_ld normalised
+    auto member = [&](const int i, omgsr_igemm_args& a) -> int {
+        a = args[i];
+        if (!a.weight) a.weight = a.weight_cm;          // (the row-major packing does not exist in this form)
+        if (!a.in_scale || !a.w_scale || !a.weight_cm) return OMGSR_E_BADARG;
+        a.group_tiles = omgsr::g_batch_invariant ? 0 : total;
+        a.workspace = nullptr;
+        return validate_args(a);
+    };
+    for (int i = 0; i < count; ++i) {                   // every member is checked before the first launch
+        omgsr_igemm_args a;
+        const int rc = member(i, a);
+        if (rc != 0) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int at = 0; at < count; at += MXC_MULTI_MAX) {
+        const int ng = count - at < MXC_MULTI_MAX ? count - at : MXC_MULTI_MAX;
+        omgsr_igemm_args grp[MXC_MULTI_MAX];
+        Geo geo[MXC_MULTI_MAX];
+        double gf = 0.0;
+        for (int i = 0; i < ng; ++i) {
+            member(at + i, grp[i]);
+            double f, b;
+            work_of(grp[i], &f, &b);
+            gf += f;
+            geo[i] = geo_of(grp[i]);
+        }
+        const int rc = ng == 1 ? omgsr::mxfp8_conv_launch(grp[0], geo[0], st, gf) : omgsr::mxfp8_conv_launch_multi(grp, geo, ng, st, gf);
+        if (rc != 0) return rc;
+    }
+    return 0;
 }
 
 extern "C" int omgsr_igemm(const omgsr_igemm_args* ap, void* stream) {

@@ -696,15 +696,17 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_mxfp8_kernel(const bf16_t* _
 // GroupNorm apply (+ SiLU) with the fp32 result written as OMGSR_EL_MXFP8 codes + scales (the operand of omgsr_conv_mxfp8, ABI v22): the
 // arithmetic of gn_apply_any_body up to the rounding, then omgsr_quantize_mxfp8's rule. A thread holds one octet; C % 32 == 0 and 256 % 4 == 0
 // keep the four octets of a 32-channel block in one lane quad in every iteration, so the block maximum is two DPP exchanges.
+// (n, bx): the tensor's row and the block's index inside it - blockIdx of the one-tensor kernel, the prefix-table lookup of the _multi one
 template <bool XF32>
-__global__ __launch_bounds__(256) void gn_apply_mxfp8_kernel(const void* __restrict__ x, unsigned char* __restrict__ codes, unsigned char* __restrict__ scales,
-                                                              const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows) {
+OMGSR_DEVINL void gn_apply_mxfp8_body(const void* __restrict__ x, unsigned char* __restrict__ codes, unsigned char* __restrict__ scales,
+                                      const float* __restrict__ mean, const float* __restrict__ rstd,
+                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                      const int64_t HW, const int C, const int G, const int act, const int64_t px_per_block, const int stat_rows,
+                                      const int n, const int bx) {
     extern __shared__ __attribute__((aligned(16))) float gn_lds[];
     float* sc = gn_lds;
     float* sh = gn_lds + C;
-    const int t = threadIdx.x, n = (int)blockIdx.y;
+    const int t = threadIdx.x;
     const int ns = n % stat_rows;
     const int cpg = C / G;
     for (int c = t; c < C; c += 256) {
@@ -716,7 +718,7 @@ __global__ __launch_bounds__(256) void gn_apply_mxfp8_kernel(const void* __restr
     }
     __syncthreads();
     const int nch8 = C >> 3;
-    const int64_t p0 = (int64_t)blockIdx.x * px_per_block;
+    const int64_t p0 = (int64_t)bx * px_per_block;
     int64_t p1 = p0 + px_per_block; if (p1 > HW) p1 = HW;
     const int total = (int)((p1 - p0) * nch8);
     const int64_t pix0 = (int64_t)n * HW + p0;
@@ -745,6 +747,23 @@ __global__ __launch_bounds__(256) void gn_apply_mxfp8_kernel(const void* __restr
         c8 += step8; px += stepp;
         if (c8 >= nch8) { c8 -= nch8; ++px; }
     }
+}
+template <bool XF32>
+__global__ __launch_bounds__(256) void gn_apply_mxfp8_kernel(const void* __restrict__ x, unsigned char* __restrict__ codes, unsigned char* __restrict__ scales,
+                                                              const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              int64_t HW, int C, int G, int act, int64_t px_per_block, int stat_rows) {
+    gn_apply_mxfp8_body<XF32>(x, codes, scales, mean, rstd, gamma, beta, HW, C, G, act, px_per_block, stat_rows, (int)blockIdx.y, (int)blockIdx.x);
+}
+// The tile-shape groups of a tiled-VAE layer in ONE launch (GnApplyMulti as gn_apply_any_multi_kernel reads it: y = codes, y2 = scales): the
+// one-tensor body on the looked-up (tensor, row, pixel range), so the bytes are those of a launch per tensor.
+template <bool XF32>
+__global__ __launch_bounds__(256) void gn_apply_mxfp8_multi_kernel(const GnApplyMulti m, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                    int C, int G, int act, int stat_rows) {
+    int n, bx;
+    const int s = gn_multi_lookup(m, n, bx);
+    gn_apply_mxfp8_body<XF32>(m.x[s], (unsigned char*)m.y[s], (unsigned char*)m.y2[s], mean, rstd, gamma, beta, m.HW[s], C, G, act, m.ppb[s], stat_rows, n, bx);
 }
 
 }  // namespace
@@ -1053,6 +1072,39 @@ extern "C" int omgsr_groupnorm_apply_mxfp8(const void* x, void* codes, void* sca
     else
         hipLaunchKernelGGL(gn_apply_mxfp8_kernel<false>, grid, dim3(256), 2 * C * sizeof(float), st, x, (unsigned char*)codes, (unsigned char*)scales, mean, rstd, gamma,
                            beta, HW, (int)C, (int)G, (int)act, ppb, (int)stat_rows);
+    return (int)hipGetLastError();
+}
+
+extern "C" int omgsr_groupnorm_apply_mxfp8_multi(const omgsr_gn_apply_group* groups, int32_t ngroups, const float* mean, const float* rstd,
+                                                 const float* gamma, const float* beta, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                                 int32_t x_el, void* stream) {
+    if (!groups || ngroups <= 0 || ngroups > OMGSR_GN_MAX_GROUPS || !mean || !rstd || C <= 0 || G <= 0 || stat_rows <= 0) return OMGSR_E_BADARG;
+    if ((x_el != OMGSR_EL_16 && x_el != OMGSR_EL_F32) || (act != OMGSR_ACT_NONE && act != OMGSR_ACT_SILU)) return OMGSR_E_BADARG;
+    if ((C % 128) || (C % G) || C > 8192 || omgsr::compute_dtype() != 0) return OMGSR_E_SHAPE;
+    GnApplyMulti m{};
+    double elems = 0.0;
+    int64_t blocks = 0;
+    for (int k = 0; k < ngroups; ++k) {
+        const omgsr_gn_apply_group& g = groups[k];
+        if (!g.x || !g.y || !g.y2 || g.rows <= 0 || g.HW <= 0 || (g.rows % stat_rows)) return OMGSR_E_BADARG;
+        m.x[k] = g.x; m.y[k] = g.y; m.y2[k] = g.y2; m.HW[k] = g.HW;
+        m.ppb[k] = gn_apply_ppb(g.rows, g.HW, C);              // each group keeps the block shape of its own launch
+        m.nblk[k] = (int)((g.HW + m.ppb[k] - 1) / m.ppb[k]);
+        m.start[k] = (int)blocks;
+        blocks += (int64_t)m.nblk[k] * g.rows;
+        if (blocks >= (1ll << 31)) return OMGSR_E_SHAPE;
+        elems += (double)g.rows * (double)g.HW * C;
+    }
+    m.start[ngroups] = (int)blocks;
+    m.count = ngroups;
+    hipStream_t st = (hipStream_t)stream;
+    omgsr::TimingScope ts(OMGSR_TK_GN, 0.0, ((x_el == OMGSR_EL_F32 ? 4.0 : 2.0) + 1.0 + 1.0 / 32.0) * elems, st);
+    if (x_el == OMGSR_EL_F32)
+        hipLaunchKernelGGL(gn_apply_mxfp8_multi_kernel<true>, dim3((unsigned)blocks), dim3(256), 2 * C * sizeof(float), st, m, mean, rstd, gamma, beta, (int)C, (int)G,
+                           (int)act, (int)stat_rows);
+    else
+        hipLaunchKernelGGL(gn_apply_mxfp8_multi_kernel<false>, dim3((unsigned)blocks), dim3(256), 2 * C * sizeof(float), st, m, mean, rstd, gamma, beta, (int)C, (int)G,
+                           (int)act, (int)stat_rows);
     return (int)hipGetLastError();
 }
 

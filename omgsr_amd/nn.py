@@ -175,14 +175,16 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
                           gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack)
 
     def nhwc_multi(self, xs, *, pad=None, upsample=False, act=ops.ACT_NONE, residuals=None, stride=None, gn_groups=0,
-                   out_dtype=ops.OUT_STREAM, out_split=1, gn=None):
-        """nhwc() of several inputs (the tile-shape groups of a tiled-VAE layer) in one launch where the kernel allows (ops.conv2d_multi)."""
+                   out_dtype=ops.OUT_STREAM, out_split=1, gn=None, fp8=False):
+        """nhwc() of several inputs (the tile-shape groups of a tiled-VAE layer) in one launch where the kernel allows (ops.conv2d_multi).
+        fp8: the caller serves marked layers (VAEHook.fp8_convs) - a marked conv then hands its MXFP8 form on under nhwc()'s condition."""
         pw = self.packed()
         p = self.padding[0] if pad is None else pad
         if out_dtype == ops.OUT_STREAM and self.out_inner16 and ops.precise():
             out_dtype = ops.OUT_BF16
+        fp8_pack = self.packed_mxfp8 if (fp8 and self.fp8 and gn is not None) else None
         return ops.conv2d_multi(list(xs), pw, stride=stride or self.stride[0], pad=p, upsample=upsample, act=act, residuals=residuals,
-                                gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn)
+                                gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack)
 
     def forward(self, x):  # NCHW compat
         y = self.nhwc(ops.nchw_to_nhwc(x.contiguous(), ops._round_up(self.in_channels, 8)))

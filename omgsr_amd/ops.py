@@ -826,16 +826,82 @@ def conv2d_mxfp8(xq: "Mxfp8", pw8: PackedWeight, *, act: int = ACT_NONE, residua
     return _conv2d_mxfp8(a, xq, pw8, out, gn_groups)
 
 
+def _mxfp8_group_tiles(arr, n: int) -> int:
+    """The group's total of spatial-form workgroup tiles (include/omgsr_hip.h, omgsr_conv_mxfp8_multi): what `group_tiles` holds when the
+    library plans a member's GroupNorm partials; 0 in batch-invariant mode (every member on its own)."""
+    if _BATCH_INVARIANT:
+        return 0
+    return sum(arr[i].N * ((arr[i].Wo + 31) // 32) * ((arr[i].Ho + 7) // 8) * ((arr[i].Cout + 127) // 128) for i in range(n))
+
+
+def _fill_conv_mxfp8(a: IgemmArgs, pw8: PackedWeight) -> None:
+    """The weight side of an argument block filled for the 16-bit form of the same problem -> the MXFP8 form's (the pointers do not enter
+    omgsr_conv_mxfp8_multi_ok's per-problem rules, but the problems of a launch must agree in them)."""
+    a.weight, a.weight_cm, a.w_scale, a.weight_ph = pw8.w_cm.data_ptr(), pw8.w_cm.data_ptr(), pw8.w_scale.data_ptr(), None
+    a.Cout_pad, a.K_pad = pw8.w_cm.shape[2], 9 * pw8.cin
+    a.bias = _ptr(pw8.bias) if a.bias is None else a.bias
+
+
+def _conv2d_mxfp8_multi(arr, n: int, xqs, pw8: PackedWeight, outs, gn_groups: int):
+    """Launch omgsr_conv_mxfp8_multi on argument blocks filled for the 16-bit form of the same problems (omgsr_conv_mxfp8_multi_ok said 1)."""
+    total = _mxfp8_group_tiles(arr, n)
+    partials = []
+    for i in range(n):
+        a, xq = arr[i], xqs[i]
+        if xq.codes.shape[-1] != pw8.cin or a.Cout != pw8.cout:
+            raise ValueError(f"conv2d_mxfp8_multi: operand K {xq.codes.shape[-1]} / Cout {a.Cout} do not match the packed weight ({pw8.cin}, {pw8.cout})")
+        a.in_, a.in_scale = xq.codes.data_ptr(), xq.scales.data_ptr()
+        _fill_conv_mxfp8(a, pw8)
+        a.workspace, a.group_tiles = None, total
+        partials.append(_conv_gn(a, gn_groups, 1, outs[i].device))
+    check(_lib.load().omgsr_conv_mxfp8_multi(arr, n, _stream()), "omgsr_conv_mxfp8_multi")
+    for out, partial in zip(outs, partials):
+        if partial is not None:
+            out._omgsr_gn = (partial, gn_groups, out.data_ptr(), out._version)
+    return outs
+
+
+def conv2d_mxfp8_multi(xqs, pw8: PackedWeight, *, act: int = ACT_NONE, residuals=None, out_dtype: int = OUT_STREAM, gn_groups: int = 0):
+    """conv2d_mxfp8 of several MXFP8 operands xqs[k] [N_k, H_k, W_k, Cin] with ONE pack_conv_weight_mxfp8 weight (the tile-shape groups of a
+    tiled-VAE layer) through omgsr_conv_mxfp8_multi: one launch of mxfp8_conv_multi_kernel per 8 problems, served as a GROUP (the sum of the
+    problems' tiles fills the chip where no problem alone does). No other kernel stands behind it: a group omgsr_conv_mxfp8_multi_ok does not
+    accept raises (OMGSR_E_SHAPE). Same bytes as one conv2d_mxfp8 call per operand where those are served. Returns the list of outputs."""
+    xqs = list(xqs)
+    if not xqs or not all(isinstance(xq, Mxfp8) for xq in xqs) or not pw8.fp8 or pw8.w_cm is None:
+        raise ValueError("conv2d_mxfp8_multi: Mxfp8 operands and a pack_conv_weight_mxfp8 weight")
+    n = len(xqs)
+    arr = (IgemmArgs * n)()
+    outs = []
+    for i, xq in enumerate(xqs):
+        N, H, W, Cin = xq.codes.shape
+        a = arr[i]
+        out = _out_tensor((N, H, W), pw8.cout, out_dtype, 1, xq.codes.device)
+        residual = None if residuals is None else residuals[i]
+        if residual is not None and tuple(residual.shape) != (N, H, W, pw8.cout):
+            raise ValueError(f"residual shape {tuple(residual.shape)} != output {(N, H, W, pw8.cout)}")
+        _fill_out(a, out, 1, residual, pw8.cout)
+        a.N, a.H, a.W, a.Cin, a.Cout = N, H, W, Cin, pw8.cout
+        a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 3, 3, 1, 1, 1, 0
+        a.Ho, a.Wo, a.act, a.out_layout = H, W, act, LAYOUT_NHWC
+        a.batch, a.alpha, a.sample_rows = 1, 1.0, H * W
+        a.overflow_flag = None
+        outs.append(out)
+    return _conv2d_mxfp8_multi(arr, n, xqs, pw8, outs, gn_groups)
+
+
 def conv2d_multi(xs, pw: PackedWeight, *, stride: int = 1, pad: tuple[int, int, int, int] | int = 1, upsample: bool = False,
                  act: int = ACT_NONE, residuals=None, out_dtype: int = OUT_STREAM, gn_groups: int = 0, out_split: int = 1,
-                 gn: Optional["GnSpec"] = None):
+                 gn: Optional["GnSpec"] = None, fp8_pack=None):
     """conv2d of several inputs with ONE weight (the tile-shape groups of a tiled-VAE layer: each x is its own dense [T*N, h, w, C]
     tensor) through omgsr_igemm_multi: the problems that take the halo-tile kernel run as one launch, with the kernel choice and the
-    fused GroupNorm statistics planned for the group. Same results as a conv2d call per input. Returns the list of outputs."""
+    fused GroupNorm statistics planned for the group. Same results as a conv2d call per input. Returns the list of outputs.
+    fp8_pack (see conv2d; needs gn and out_split 1): where omgsr_conv_mxfp8_multi_ok accepts the GROUP, the layer is one apply-to-MXFP8
+    launch (group_norm_apply_mxfp8_multi) and one mxfp8_conv_multi_kernel launch; otherwise the WHOLE layer takes the 16-bit path below
+    exactly as without it - one form per layer, tiles of one image never see different arithmetic."""
     n = len(xs)
     if n == 1:
         return [conv2d(xs[0], pw, stride=stride, pad=pad, upsample=upsample, act=act, residual=None if residuals is None else residuals[0],
-                       out_dtype=out_dtype, gn_groups=gn_groups, out_split=out_split, gn=gn)]
+                       out_dtype=out_dtype, gn_groups=gn_groups, out_split=out_split, gn=gn, fp8_pack=fp8_pack)]
     lib = _lib.load()
     if gn is not None and not all(_gn_candidate(x, pw) for x in xs):
         xs, gn = [gn.apply(x, pw.split) for x in xs], None
@@ -848,6 +914,11 @@ def conv2d_multi(xs, pw: PackedWeight, *, stride: int = 1, pad: tuple[int, int, 
         outs.append(out)
         if gn is not None:
             arr[i].in_el = EL_16
+    if fp8_pack is not None and gn is not None and out_split == 1 and lib.omgsr_conv_mxfp8_multi_ok(arr, n):
+        xqs = []
+        for k in range(0, n, _lib.GN_MAX_GROUPS):
+            xqs += group_norm_apply_mxfp8_multi(keep[k:k + _lib.GN_MAX_GROUPS], gn.mean, gn.rstd, gn.gamma, gn.beta, gn.groups, gn.act)
+        return _conv2d_mxfp8_multi(arr, n, xqs, fp8_pack(), outs, gn_groups)
     check(lib.omgsr_igemm_multi_plan(arr, n), "omgsr_igemm_multi_plan")
     if out_split == 4 and not all(lib.omgsr_igemm_out_mx6_ok(C.byref(arr[i])) for i in range(n)):
         ys = conv2d_multi(keep, pw, stride=stride, pad=pad, upsample=upsample, act=act, residuals=residuals, out_dtype=OUT_STREAM, gn=gn)
@@ -1311,6 +1382,29 @@ def group_norm_apply_mxfp8(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tens
     check(_lib.load().omgsr_groupnorm_apply_mxfp8(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
                                                   _ptr(beta), rows, HW, Cc, groups, act, mean.shape[0], xel, _stream()), "omgsr_groupnorm_apply_mxfp8")
     return Mxfp8(codes, scales)
+
+
+def group_norm_apply_mxfp8_multi(xs, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE):
+    """group_norm_apply_mxfp8 over the tile-shape groups of one tiled-VAE layer in ONE launch (omgsr_groupnorm_apply_mxfp8_multi): xs[k] is
+    [T_k*N, h_k, w_k, C] (tile-major), all of one channel count and element kind. Returns the list of Mxfp8; the bytes are those of one
+    group_norm_apply_mxfp8 call per tensor."""
+    if not 0 < len(xs) <= _lib.GN_MAX_GROUPS:
+        raise ValueError(f"1 ... {_lib.GN_MAX_GROUPS} tile shape groups")
+    xel = _el(xs[0], "x")
+    Cc = xs[0].shape[-1]
+    if any(_el(x, "x") != xel or x.shape[-1] != Cc for x in xs):
+        raise ValueError("group_norm_apply_mxfp8_multi: one channel count and element kind per launch")
+    if Cc % 128:
+        raise ValueError(f"group_norm_apply_mxfp8_multi: C = {Cc} is not a multiple of 128")
+    outs = [Mxfp8(torch.empty(x.shape, device=x.device, dtype=torch.uint8),
+                  torch.empty((*x.shape[:-1], Cc // 32), device=x.device, dtype=torch.uint8)) for x in xs]
+    desc = (_lib.GnApplyGroup * len(xs))()
+    for k, x in enumerate(xs):
+        desc[k].x, desc[k].y, desc[k].y2 = x.data_ptr(), outs[k].codes.data_ptr(), outs[k].scales.data_ptr()
+        desc[k].rows, desc[k].HW = x.shape[0], x.numel() // (x.shape[0] * Cc)
+    check(_lib.load().omgsr_groupnorm_apply_mxfp8_multi(desc, len(xs), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta), Cc, groups, act,
+                                                        mean.shape[0], xel, _stream()), "omgsr_groupnorm_apply_mxfp8_multi")
+    return outs
 
 
 def group_norm(x: torch.Tensor, gamma, beta, groups: int, eps: float, act: int = ACT_NONE, split: int = 1, also_cast: int = 0):

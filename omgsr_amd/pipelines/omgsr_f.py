@@ -48,7 +48,8 @@ class OMGSR_F_Infer(torch.nn.Module):
         # precision_policy={"flux": {"fp8": [patterns]}} narrows the list). Modules are held and LoRA-merged in bf16, their fp8 forms packed lazily.
         # precision_policy={"flux": {"fp8_attention": True | [block patterns]}} (fp8 tier only, opt-in) also runs those blocks' joint attention
         # on MXFP8 q / k / V^T (precision.set_fp8_attention). precision_policy={"vae": {"fp8": True | [layer patterns]}} (fp8 tier only, opt-in)
-        # runs those resnet convs of the VAE as MXFP8 convolutions where the kernel serves them (precision.set_fp8_conv); the tiled VAE is not served.
+        # runs those resnet convs of the VAE as MXFP8 convolutions where the kernel serves them (precision.set_fp8_conv); the tiled VAE serves them with
+        # _init_tiled_vae(fp8_convs=True) only.
         fp8 = weight_dtype == torch.float8_e4m3fn
         if fp8 and precision_policy is not None and not (isinstance(precision_policy, dict) and set(precision_policy) <= {"flux", "vae"} and
                                                          isinstance(precision_policy.get("flux", {}), dict) and
@@ -128,15 +129,22 @@ class OMGSR_F_Infer(torch.nn.Module):
         return self._graph_params()
 
     def _init_tiled_vae(self, encoder_tile_size=256, decoder_tile_size=256, fast_decoder=False, fast_encoder=False,
-                        color_fix=False, vae_to_gpu=True):
-        if getattr(self, "fp8_vae", False):
-            raise ValueError("the tiled VAE is not served by the fp8 VAE convolutions (precision_policy {'vae': {'fp8': ...}}): its launch groups "
-                             "run the bf16 kernels only - build the pipeline without that key to tile")
+                        color_fix=False, vae_to_gpu=True, fp8_convs=False):
+        """fp8_convs=True (needs precision_policy {'vae': {'fp8': ...}}): the hooks serve the marked convs with the MXFP8 kernels, one form per
+        layer (VAEHook.fp8_convs). Without it the key and the tiled VAE stay exclusive."""
+        fp8_vae = getattr(self, "fp8_vae", False)
+        if fp8_vae and not fp8_convs:
+            raise ValueError("the tiled VAE is not served by the fp8 VAE convolutions (precision_policy {'vae': {'fp8': ...}}) unless asked: its "
+                             "launch groups run the bf16 kernels - pass fp8_convs=True to serve them in MXFP8, or build the pipeline without "
+                             "that key to tile")
+        if fp8_convs and not fp8_vae:
+            raise ValueError("fp8_convs=True needs the fp8 tier with precision_policy {'vae': {'fp8': True | [layer patterns]}}: no VAE conv is marked")
         from .vaehook import VAEHook
         self.vae.encoder._tile_hook = VAEHook(self.vae.encoder, encoder_tile_size, is_decoder=False, fast_decoder=fast_decoder,
                                               fast_encoder=fast_encoder, color_fix=color_fix, to_gpu=vae_to_gpu)
         self.vae.decoder._tile_hook = VAEHook(self.vae.decoder, decoder_tile_size, is_decoder=True, fast_decoder=fast_decoder,
                                               fast_encoder=fast_encoder, color_fix=color_fix, to_gpu=vae_to_gpu)
+        self.vae.encoder._tile_hook.fp8_convs = self.vae.decoder._tile_hook.fp8_convs = bool(fp8_convs)
 
     def _velocity_tokens(self, z_nhwc, prompt_embeds, pooled, text_ids, image_ids):
         """z [B,t,t,16] -> (packed tokens, velocity tokens) [B, t*t/4, 64]."""

@@ -14,6 +14,8 @@ with 288 GB of HBM:
   * mid-block attention stays tile-local, valid regions are cropped and pasted without blending
 Fast mode (fast_encoder / fast_decoder) estimates every GroupNorm's statistics once on a nearest-exact
 down-sampled, re-standardised copy of the whole input, then all tiles use those fixed statistics.
+With `fp8_convs` (the fp8 tier, opt-in) the marked 3x3 convs of a layer whose tile-shape groups the MXFP8 kernels serve as a group run as one
+apply-to-MXFP8 launch and one mxfp8_conv_multi_kernel launch; the estimate pass (one tensor) routes like an untiled call.
 """
 from __future__ import annotations
 
@@ -56,6 +58,11 @@ def split_tiles(h: int, w: int, tile_size: int, pad: int, is_decoder: bool) -> T
 
 
 class VAEHook:
+    # the fp8 tier's opt-in VAE convolutions (precision.set_fp8_conv marks; OMGSR_F_Infer._init_tiled_vae(fp8_convs=True) sets this): the marked
+    # convs hand their MXFP8 form to ops.conv2d_multi, which serves a layer's tile-shape groups as ONE group or not at all. False: a marked
+    # VAE runs the 16-bit kernels here, bit for bit as an unmarked one
+    fp8_convs = False
+
     def __init__(self, net, tile_size, is_decoder, fast_decoder, fast_encoder, color_fix, to_gpu=False):
         self.net = net                      # omgsr_amd Encoder | Decoder
         self.tile_size = tile_size
@@ -165,7 +172,7 @@ class VAEHook:
                         groups[k] = y
             elif kind == "conv":
                 keys = list(groups)
-                for k, y in zip(keys, op[1].nhwc_multi([groups[k] for k in keys], gn=pending, **op[2])):
+                for k, y in zip(keys, op[1].nhwc_multi([groups[k] for k in keys], gn=pending, fp8=self.fp8_convs, **op[2])):
                     groups[k] = y
                 pending = None
             elif kind == "res_push":
@@ -175,9 +182,9 @@ class VAEHook:
                 keys = list(groups)
                 xs, rs = [groups[k] for k in keys], [res[k].pop() for k in keys]
                 if op[3] is not None:
-                    outs = op[1].nhwc_multi(xs, residuals=rs, out_dtype=ops.OUT_BF16, out_split=op[3].in_split(), gn=pending)
+                    outs = op[1].nhwc_multi(xs, residuals=rs, out_dtype=ops.OUT_BF16, out_split=op[3].in_split(), gn=pending, fp8=self.fp8_convs)
                 else:
-                    outs = op[1].nhwc_multi(xs, residuals=rs, gn_groups=op[2], gn=pending)
+                    outs = op[1].nhwc_multi(xs, residuals=rs, gn_groups=op[2], gn=pending, fp8=self.fp8_convs)
                 pending = None
                 for k, y in zip(keys, outs):
                     groups[k] = y

@@ -7,7 +7,13 @@
     the key, same process, alternated rounds;
   * quality (--quality): full depth, OMGSR-F 256 -> 1024, batch 1, seeded draws, the fp8 tier with and without the key against the accurate tier.
 
-    python tools/bench_fp8_vae.py [--rounds 3] [--no-step] [--quality] [--out profiles/fp8_vae.json]
+  * tiled (--tiled; nothing else runs): the FLUX VAE's TILED decode (VAEHook, decoder tile 64: tile shapes 86 / 64 latents) of a 128 x 128
+    latent, batch 8 - the 16-bit tiled decode against the fp8 tiled decode (the marked layers' tile-shape groups through
+    gn_apply_mxfp8_multi_kernel + mxfp8_conv_multi_kernel), same process, alternated rounds, HIP events; and the kind-1 launches of one decode
+    per arm by timing variant (21 / 22 / others). With --quality: the seeded full-depth draws above with both VAEs tiled (encoder tile 512,
+    decoder tile 64), the fp8 tier with and without the key (default list) against the accurate tier.
+
+    python tools/bench_fp8_vae.py [--rounds 3] [--no-step] [--quality] [--tiled] [--out profiles/fp8_vae.json]
 """
 from __future__ import annotations
 
@@ -168,6 +174,103 @@ def quality(dev, draws: int) -> list:
     return rows
 
 
+def _variant_counts(fn) -> dict:
+    """Kind-1 (conv / GEMM) launches of one fn() call by timing variant: {"21": n, "22": n, "others": n}, and the number of layers they stand for."""
+    import torch
+    from omgsr_amd import _lib
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    lib.omgsr_timing_enable(1)
+    lib.omgsr_timing_reset()
+    try:
+        fn()
+        buf = (_lib.TimingEntry * 8192)()
+        n = lib.omgsr_timing_collect(buf, 8192)
+    finally:
+        lib.omgsr_timing_enable(0)
+    v = [e.variant for e in buf[:n] if e.kind == 1]
+    return {"21": v.count(21), "22": v.count(22), "others": len(v) - v.count(21) - v.count(22)}
+
+
+def tiled_decode(dev, batch: int, rounds: int, iters: int) -> dict:
+    """FLUX VAE tiled decode, 128 x 128 latent, decoder tile 64: one VAE, one hook; the arms differ in the hook's fp8_convs only (the marks and
+    both weight packs stay), so they alternate without re-packing."""
+    import torch
+    from omgsr_amd.diffusers_api import AutoencoderKL, FLUX_VAE_CONFIG
+    from omgsr_amd.pipelines.vaehook import VAEHook
+    from omgsr_amd.precision import fp8_conv_layers, set_fp8_conv
+    from omgsr_amd.testing import seeded_init_
+    vae = seeded_init_(AutoencoderKL(**FLUX_VAE_CONFIG), 303, rounded=False).to(dev, torch.bfloat16).eval()
+    marked = set_fp8_conv(vae, True)
+    hook = VAEHook(vae.decoder, 64, is_decoder=True, fast_decoder=False, fast_encoder=False, color_fix=False)
+    z = torch.randn(batch, 128, 128, 16, generator=torch.Generator().manual_seed(77)).to(dev, torch.bfloat16)
+    arms = {"bf16_tiled": False, "fp8_tiled": True}
+    t = {k: [] for k in arms}
+    counts = {}
+    with torch.no_grad():
+        for k, on in arms.items():
+            hook.fp8_convs = on
+            hook(z); hook(z)                        # warm: packs, code objects
+            counts[k] = _variant_counts(lambda: hook(z))
+        for r in range(rounds):
+            for k in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+                hook.fp8_convs = arms[k]
+                hook(z)
+                t[k].append(_events_ms(lambda: hook(z), iters))
+            print(f"round {r}: " + ", ".join(f"{k} {t[k][-1]:.2f} ms" for k in arms), flush=True)
+    out = dict(shape=dict(latent=128, batch=batch, decoder_tile=64, tile_shapes=[86, 64]), marked_layers=marked, layers=fp8_conv_layers(vae),
+               iters_per_round=iters, bf16_tiled_ms=[round(v, 3) for v in t["bf16_tiled"]], fp8_tiled_ms=[round(v, 3) for v in t["fp8_tiled"]],
+               speedup_median=round(statistics.median(t["bf16_tiled"]) / statistics.median(t["fp8_tiled"]), 3),
+               fp8_faster_in_every_round=all(a > c for a, c in zip(t["bf16_tiled"], t["fp8_tiled"])),
+               kind1_launches_by_variant=counts)
+    return out
+
+
+def tiled_quality(dev, draws: int) -> list:
+    """quality()'s seeded draws with both VAEs tiled (encoder tile 512: the 1024^2 input splits into 2 x 2 tiles; decoder tile 64), default list."""
+    import torch
+    from omgsr_amd import ops
+    from omgsr_amd.diffusers_api import AutoencoderKL, FLUX_VAE_CONFIG, FluxTransformer2DModel
+    from omgsr_amd.pipelines.omgsr_f import OMGSR_F_Infer, prepare_latent_image_ids
+    from omgsr_amd.testing import psnr, rel_l2, seeded_init_, seeded_init_device_, synthetic_lq
+    rows = []
+    for draw in range(draws):
+        ops.set_compute_dtype(torch.float32)
+        with torch.device("meta"):
+            pf = FluxTransformer2DModel()
+        pf = pf.to_empty(device=dev)
+        seeded_init_device_(pf, 404 + 31 * draw)
+        pf.round_timestep_to_weight_dtype = False
+        vae_sd = seeded_init_(AutoencoderKL(**FLUX_VAE_CONFIG), 303 + 31 * draw, rounded=False).state_dict()
+        g = torch.Generator().manual_seed(4321 + draw)
+        x = synthetic_lq(1, 1024, 1024, seed=1234 + draw).to(dev)
+        eps = torch.randn(1, 16, 128, 128, generator=torch.Generator().manual_seed(99 + draw)).to(dev)
+        pe, pooled = torch.randn(1, 512, 4096, generator=g).to(dev), torch.randn(1, 768, generator=g).to(dev)
+        tids, iids = torch.zeros(512, 3, device=dev), prepare_latent_image_ids(64, 64, dev, torch.float32)
+
+        def run(wd, policy=None):
+            pv = AutoencoderKL(**FLUX_VAE_CONFIG)
+            pv.load_state_dict(vae_sd)
+            pipe = OMGSR_F_Infer(None, None, dev, wd, 244, 1.0, vae=pv, flux_transformer=pf, precision_policy=policy)
+            pipe._init_tiled_vae(encoder_tile_size=512, decoder_tile_size=64, fp8_convs=policy is not None)
+            pipe.vae.posterior_noise = eps
+            cd = torch.float32 if wd == torch.float32 else torch.bfloat16
+            with torch.no_grad():
+                return pipe(x.to(cd), pe.to(cd), pooled.to(cd), tids.to(cd), iids.to(cd), 128, 64)[0].float()
+
+        ref = run(torch.float32)
+        row = dict(draw=draw)
+        for name, pol in (("fp8_tier_tiled", None), ("vae_fp8_true_tiled", {"vae": {"fp8": True}})):
+            y = run(torch.float8_e4m3fn, pol)
+            row[name] = dict(rel_l2=rel_l2(y, ref), psnr_db=round(psnr(y, ref), 2))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del pf
+        torch.cuda.empty_cache()
+    ops.set_compute_dtype(torch.bfloat16)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=3)
@@ -177,6 +280,8 @@ def main():
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--quality", action="store_true", help="also the full-depth quality draws (minutes)")
     ap.add_argument("--draws", type=int, default=3)
+    ap.add_argument("--tiled", action="store_true", help="the tiled VAE decode legs only (with --quality: the tiled full-depth draws)")
+    ap.add_argument("--iters", type=int, default=5, help="--tiled: decodes per timed window")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp8_vae.json"))
     args = ap.parse_args()
     import torch
@@ -188,6 +293,13 @@ def main():
     if os.path.isfile(args.out):                    # sections measured by an earlier call stay
         with open(args.out) as f:
             rec = {**json.load(f), **rec}
+    if args.tiled:
+        rec["tiled_decode_b%d" % args.batch] = tiled_decode(dev, args.batch, args.rounds, args.iters)
+        print(json.dumps(rec["tiled_decode_b%d" % args.batch]), flush=True)
+        if args.quality:
+            rec["tiled_full_depth_quality"] = tiled_quality(dev, args.draws)
+        args.no_layers = args.no_step = True
+        args.quality = False
     if not args.no_layers:
         rec["layers"] = layer_table(dev, args.batch, args.rounds)
     if not args.no_step:
