@@ -83,6 +83,8 @@ CONV_CASES = [
     (1, 64, 16, 256, 200, 1, (1, 1, 1, 1), False, False, True, 1),
     (2, 32, 32, 100, 260, 1, (1, 1, 1, 1), True, True, False, 0),
     # convs that miss the halo kernel and take the ping-pong GEMM kernel's implicit-GEMM form (K >= 1536, >= 128 tiles of 256 x 256)
+    # (today igemm_p8_ok takes GEMM-shaped problems only: these run the LDS-DMA kernel, whole or split over K - tests/test_guard_bands_gpu.py
+    # pins the variant every form really runs)
     (72, 256, 512, 16, 16, 1, (1, 1, 1, 1), False, True, True, 0),     # 16-wide maps (UNet 16 x 16 level)
     (8, 256, 256, 128, 128, 2, (0, 1, 0, 1), False, True, False, 0),   # VAE down-sampling conv
     (9, 192, 256, 118, 122, 2, (1, 1, 1, 1), False, True, False, 1),   # stride 2, ragged, 33 792 rows (last tile partial)
@@ -501,6 +503,30 @@ def test_layout_and_latent_ops():
     assert torch.equal(tok.float().cpu(), ref_tok)
     un = ops.flux_unpack(tok, 8, 12)
     assert torch.equal(un.float().cpu(), lat)
+
+
+@pytest.mark.parametrize("H,W,tile", [(86, 150, 64), (200, 312, 96), (37, 41, 12), (100, 260, 64), (128, 128, 64)])
+def test_resize_nearest_exact(H, W, tile):
+    """ops.resize_nearest_exact (the tiled VAE's fast-mode down-sampling) against F.interpolate(mode="nearest-exact") on the CPU, byte for byte,
+    with the scale factor formed as VAEHook._estimate forms it. At the four ragged shapes ATen's source index differs from the in / out ratio
+    formula in 25, 44, 8 and 18 row / column indices and from plain `nearest` in every row; every pixel of the input carries its own value (the
+    base-4 digits of its index over the 8 channels, plus 4 per image: 0 .. 7, exact in every element type), so a wrong index cannot collide."""
+    ops = _ops()
+    N, Cc = 2, 8
+    s = tile / max(H, W)
+    idx = torch.arange(H * W).reshape(1, H, W, 1) // (4 ** torch.arange(Cc)).reshape(1, 1, 1, Cc) % 4
+    x = (idx + 4 * torch.arange(N).reshape(N, 1, 1, 1)).float()                  # NHWC
+    assert H * W <= 4 ** Cc and x.reshape(N * H * W, Cc).unique(dim=0).shape[0] == N * H * W
+    ref = F.interpolate(x.permute(0, 3, 1, 2), scale_factor=s, mode="nearest-exact").permute(0, 2, 3, 1).contiguous()
+    Ho, Wo = math.floor(H * s), math.floor(W * s)
+    assert tuple(ref.shape) == (N, Ho, Wo, Cc)
+    y = ops.resize_nearest_exact(bf(x).to(DEV), s)                                # the 16-bit stream
+    assert tuple(y.shape) == (N, Ho, Wo, Cc) and y.dtype == ops.act_dtype()
+    assert torch.equal(y.cpu(), bf(ref))
+    ops.set_compute_dtype(torch.float32)                                          # fp32 stream tensors: the accurate tier (the fixture restores the tier)
+    y32 = ops.resize_nearest_exact(x.to(DEV), s)
+    assert tuple(y32.shape) == (N, Ho, Wo, Cc) and y32.dtype == torch.float32
+    assert torch.equal(y32.cpu(), ref)
 
 
 def test_tile_stitch_ops():
