@@ -367,7 +367,9 @@ int omgsr_transpose_split(const float* x, void* y, int32_t B, int32_t L, int32_t
  * D in {64, 128, 512}; Lk arbitrary (keys >= Lk are masked); kv_bstride 0 broadcasts one K/V to all B.
  * D = 512 (ABI v20, vae_attn_kernel: the VAE mid block's one-head attention, any H >= 1, no limit on Lk): 16-bit operands, o plain or the
  * two-term split (o_lo_off), q / k plain or two-term splits (q_lo_off / k_lo_off, the D = 64 semantics); 16-byte aligned q / k / vt, 8-byte
- * aligned o; p_split, vt_lo_off and o_mx return OMGSR_E_SHAPE. k rows and vt columns >= Lk are never used.
+ * aligned o. p_split and vt_lo_off (> 0, % 8 == 0) come TOGETHER and with split q / k: every operand a two-term split, the D = 64 arithmetic
+ * (vae_attn_full_kernel, the range-fallback tier; no field or symbol added: the ABI version does not move). One of the two without the
+ * other, either without split q / k, and o_mx return OMGSR_E_SHAPE. k rows and vt columns >= Lk are never used.
  */
 typedef struct omgsr_attn_args {
     const void* q; const void* k; const void* vt; void* o;
@@ -538,7 +540,7 @@ int omgsr_timing_reset(void);
  * kernel's split-K (chunk ranges as one igemm_halo_multi_kernel launch + splitk_reduce_kernel), 13 / 14 / 15 the halo kernel with fp6
  * (OMGSR_EL_MX6) correction chunks: single, launch group, split-K, 16 / 17 the same in the phase-decomposed form: single, launch group,
  * 18 mxfp8_gemm_kernel (ABI v18), 21 mxfp8_conv_kernel (ABI v22), 22 mxfp8_conv_multi_kernel (several problems of one layer in one launch).
- * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19), 20 vae_attn_kernel (ABI v20, D = 512). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
+ * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19), 20 vae_attn_kernel (ABI v20, D = 512), 23 vae_attn_full_kernel (D = 512, every operand a two-term split). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;
 int omgsr_timing_collect(omgsr_timing_entry* out, int cap);

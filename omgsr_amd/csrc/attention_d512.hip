@@ -15,6 +15,12 @@
 //  * V^T goes through registers (16-byte loads, masked past Lk so that padding never reaches an MFMA: 0 * NaN), rows padded to 72 B
 //    (18 banks: conflict-free ds_read_b64); it is loaded at the top of a tile and written to the other stage after the tile's MFMAs.
 //  * one barrier per tile.
+//
+// FULL (vae_attn_full_kernel, timing variant 23: the range-fallback tier, omgsr_attn_args.p_split with vt_lo_off): every operand a two-term
+// split. On top of the split q / k, V^T_lo (vp + vt_lo_off) is staged next to V^T_hi with the same pitch and the same masking, the probabilities
+// are split in place from the fp32 score registers (p_hi = (T)e, p_lo = (T)(e - p_hi), the row sum from the fp32 e), and a channel block runs
+// three PV passes, the two correction products first: O^T += V_hi^T P_lo^T + V_lo^T P_hi^T + V_hi^T P_hi^T. NCH = 64 (8 parts per query tile):
+// two stages of [K_hi | K_lo | V^T_hi | V^T_lo] are 2 (65536 + 2 * 64 * 72) = 149504 B; NCH = 128 would need 167936 B.
 #include "common.hip.h"
 #include "../../include/omgsr_hip.h"
 #include "timing.hip.h"
@@ -38,12 +44,13 @@ OMGSR_DEVINL void glds16_row(const unsigned voff, const void* sbase, const unsig
         : "memory");
 }
 
-template <typename T, int NCH, bool SPLIT>
-__global__ __launch_bounds__(256, 1) void vae_attn_kernel(const omgsr_attn_args p, const int ntiles, const float defer, const int qtiles, const int xcd_order) {
+template <typename T, int NCH, bool SPLIT, bool FULL>
+OMGSR_DEVINL void vae_attn_body(const omgsr_attn_args& p, const int ntiles, const float defer, const int qtiles, const int xcd_order) {
+    static_assert(SPLIT || !FULL, "split P / V^T come with split q / k");
     constexpr int NPART = D / NCH;
     constexpr int KT_BYTES = SPLIT ? 2 * K_BYTES : K_BYTES;          // [K_hi | K_lo] of a tile
     constexpr int V_BYTES = NCH * VP;
-    constexpr int STAGE = KT_BYTES + V_BYTES;
+    constexpr int STAGE = KT_BYTES + (FULL ? 2 * V_BYTES : V_BYTES);  // ... then [V^T_hi | V^T_lo]
     constexpr int NVC = NCH * 4 / 256;          // 16-byte V^T chunks per thread
     constexpr int NKS = D / 16, NDB = NCH / 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -95,26 +102,31 @@ __global__ __launch_bounds__(256, 1) void vae_attn_kernel(const omgsr_attn_args 
             if constexpr (SPLIT) glds16_row(voff, src + (int64_t)p.k_lo_off * 2, __builtin_amdgcn_readfirstlane(dst + K_BYTES));
         }
     };
-    u32x4_t vreg[NVC];
+    u32x4_t vreg[NVC], vregl[FULL ? NVC : 1];
+    // eight keys of a V^T row, zero past Lk
+    auto load_v8 = [&](const T* src, const int nvalid) {
+        u32x4_t v = {0u, 0u, 0u, 0u};
+        if (nvalid > 0) {
+            v = *reinterpret_cast<const u32x4_t*>(src);
+            if (nvalid < 8) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    if (2 * w >= nvalid) v[w] = 0u;
+                    else if (2 * w + 1 >= nvalid) v[w] &= 0xffffu;
+                }
+            }
+        }
+        return v;
+    };
     auto load_v = [&](const int kt) {
 #pragma unroll
         for (int i = 0; i < NVC; ++i) {
             const int c = t + 256 * i;
             const int drow = c >> 2, kc = c & 3;
             const int key0 = kt * KT + kc * 8;
-            const int nvalid = p.Lk - key0;
-            u32x4_t v = {0u, 0u, 0u, 0u};
-            if (nvalid > 0) {
-                v = *reinterpret_cast<const u32x4_t*>(vp + (int64_t)drow * p.vt_ld + key0);
-                if (nvalid < 8) {
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        if (2 * w >= nvalid) v[w] = 0u;
-                        else if (2 * w + 1 >= nvalid) v[w] &= 0xffffu;
-                    }
-                }
-            }
-            vreg[i] = v;
+            const T* src = vp + (int64_t)drow * p.vt_ld + key0;
+            vreg[i] = load_v8(src, p.Lk - key0);
+            if constexpr (FULL) vregl[i] = load_v8(src + p.vt_lo_off, p.Lk - key0);
         }
     };
     auto write_v = [&](const int buf) {
@@ -125,6 +137,10 @@ __global__ __launch_bounds__(256, 1) void vae_attn_kernel(const omgsr_attn_args 
             unsigned char* d = Vs + (c >> 2) * VP + (c & 3) * 16;      // 8-byte aligned only
             *reinterpret_cast<u32x2_t*>(d) = (u32x2_t){vreg[i][0], vreg[i][1]};
             *reinterpret_cast<u32x2_t*>(d + 8) = (u32x2_t){vreg[i][2], vreg[i][3]};
+            if constexpr (FULL) {
+                *reinterpret_cast<u32x2_t*>(d + V_BYTES) = (u32x2_t){vregl[i][0], vregl[i][1]};
+                *reinterpret_cast<u32x2_t*>(d + V_BYTES + 8) = (u32x2_t){vregl[i][2], vregl[i][3]};
+            }
         }
     };
 
@@ -218,22 +234,40 @@ __global__ __launch_bounds__(256, 1) void vae_attn_kernel(const omgsr_attn_args 
         l_run += rs;
 
         // P^T operand: score registers converted in place (key permutation, see header)
-        x8_t<T> pf[2];
+        x8_t<T> pf[2], pfl[FULL ? 2 : 1];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int j = 0; j < 8; ++j) pf[u][j] = (T)s[8 * u + j];
+        if constexpr (FULL) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pfl[u][j] = (T)(s[8 * u + j] - (float)pf[u][j]);
+        }
 
         // O^T += V^T P^T
 #pragma unroll
         for (int db = 0; db < NDB; ++db) {
             const unsigned char* vr = Vs + (32 * db + l31) * VP + 8 * half;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const u32x2_t lo = *reinterpret_cast<const u32x2_t*>(vr + 32 * u);
-                const u32x2_t hi = *reinterpret_cast<const u32x2_t*>(vr + 32 * u + 16);
+            // the 16 keys of half-tile u of this lane's channel row: two 8-byte reads (key permutation, see header)
+            auto v_frag = [&](const unsigned char* a) {
+                const u32x2_t lo = *reinterpret_cast<const u32x2_t*>(a);
+                const u32x2_t hi = *reinterpret_cast<const u32x2_t*>(a + 16);
                 const u32x4_t both = {lo[0], lo[1], hi[0], hi[1]};
-                o[db] = mfma32(__builtin_bit_cast(x8_t<T>, both), pf[u], o[db]);
+                return __builtin_bit_cast(x8_t<T>, both);
+            };
+            if constexpr (FULL) {       // the two correction products first, as in the score passes
+                const x8_t<T> vh[2] = {v_frag(vr), v_frag(vr + 32)}, vl[2] = {v_frag(vr + V_BYTES), v_frag(vr + V_BYTES + 32)};
+#pragma unroll
+                for (int u = 0; u < 2; ++u) o[db] = mfma32(vh[u], pfl[u], o[db]);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) o[db] = mfma32(vl[u], pf[u], o[db]);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) o[db] = mfma32(vh[u], pf[u], o[db]);
+            } else {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) o[db] = mfma32(v_frag(vr + 32 * u), pf[u], o[db]);
             }
         }
         if (more) write_v(buf ^ 1);
@@ -264,14 +298,32 @@ __global__ __launch_bounds__(256, 1) void vae_attn_kernel(const omgsr_attn_args 
     }
 }
 
-template <int NCH, bool SPLIT>
+// <compute type, channels per workgroup, two-term-split q / k>
+template <typename T, int NCH, bool SPLIT>
+__global__ __launch_bounds__(256, 1) void vae_attn_kernel(const omgsr_attn_args p, const int ntiles, const float defer, const int qtiles, const int xcd_order) {
+    vae_attn_body<T, NCH, SPLIT, false>(p, ntiles, defer, qtiles, xcd_order);
+}
+
+// every operand a two-term split (FULL)
+template <typename T, int NCH>
+__global__ __launch_bounds__(256, 1) void vae_attn_full_kernel(const omgsr_attn_args p, const int ntiles, const float defer, const int qtiles, const int xcd_order) {
+    vae_attn_body<T, NCH, true, true>(p, ntiles, defer, qtiles, xcd_order);
+}
+
+template <typename T, int NCH, bool SPLIT, bool FULL>
+constexpr auto vae_attn_fn() {
+    if constexpr (FULL) return &vae_attn_full_kernel<T, NCH>;
+    else return &vae_attn_kernel<T, NCH, SPLIT>;
+}
+
+template <int NCH, bool SPLIT, bool FULL = false>
 int launch_vae_attn(const omgsr_attn_args& a, hipStream_t st, const float defer) {
-    constexpr int LDS = 2 * ((SPLIT ? 2 : 1) * K_BYTES + NCH * VP);
+    constexpr int LDS = 2 * ((SPLIT ? 2 : 1) * K_BYTES + (FULL ? 2 : 1) * NCH * VP);
     static_assert(LDS <= 160 * 1024, "two stages must fit the LDS");
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vae_attn_kernel<bf16_t, NCH, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(vae_attn_kernel<f16_t, NCH, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vae_attn_fn<bf16_t, NCH, SPLIT, FULL>()), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(vae_attn_fn<f16_t, NCH, SPLIT, FULL>()), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
@@ -282,7 +334,7 @@ int launch_vae_attn(const omgsr_attn_args& a, hipStream_t st, const float defer)
     if (blocks > 0x7fffffffll) return OMGSR_E_SHAPE;
     static const char* xo = getenv("OMGSR_ATTN_XCD");            // A/B runs: "0" = natural block order
     const int xcd_order = !(xo && xo[0] == '0');
-    OMGSR_DISPATCH_T(hipLaunchKernelGGL((vae_attn_kernel<T, NCH, SPLIT>), dim3((unsigned)blocks), dim3(256), LDS, st, a, ntiles, defer, qtiles, xcd_order));
+    OMGSR_DISPATCH_T(hipLaunchKernelGGL((vae_attn_fn<T, NCH, SPLIT, FULL>()), dim3((unsigned)blocks), dim3(256), LDS, st, a, ntiles, defer, qtiles, xcd_order));
     return (int)hipGetLastError();
 }
 
@@ -291,16 +343,20 @@ int launch_vae_attn(const omgsr_attn_args& a, hipStream_t st, const float defer)
 namespace omgsr {
 // omgsr_attention with D = 512 and 16-bit operands (the caller has checked the pointers, the leading dimensions' alignment and o_lo_off)
 int vae_attention(const omgsr_attn_args& a, hipStream_t st, const float defer) {
-    // ABI v20: plain or two-term-split q / k, single or two-term-split output; no split P, no split V^T, no MX output at this head size
-    if (a.o_mx || a.p_split || a.vt_lo_off) return OMGSR_E_SHAPE;
+    // plain or two-term-split q / k, single or two-term-split output; split P and split V^T come together and with split q / k (the
+    // range-fallback tier's form: vae_attn_full_kernel); no MX output at this head size
+    if (a.o_mx) return OMGSR_E_SHAPE;
     const bool split = a.q_lo_off != 0 || a.k_lo_off != 0;
     if (split && (a.q_lo_off <= 0 || a.k_lo_off <= 0 || (a.q_lo_off & 7) || (a.k_lo_off & 7))) return OMGSR_E_SHAPE;
+    const bool full = a.p_split != 0 || a.vt_lo_off != 0;
+    if (full && (!split || !a.p_split || a.vt_lo_off <= 0 || (a.vt_lo_off & 7))) return OMGSR_E_SHAPE;
     const auto mis = [](const void* ptr) { return ((size_t)ptr & 15) != 0; };
     if (mis(a.q) || mis(a.k) || mis(a.vt) || ((size_t)a.o & 7) || (a.q_bstride & 7) || (a.k_bstride & 7) || (a.vt_bstride & 7) || (a.o_bstride & 3)) return OMGSR_E_SHAPE;
     const double flops = 4.0 * (double)a.B * a.H * (double)a.Lq * a.Lk * a.D;
-    const double bytes = 2.0 * (double)a.B * a.H * a.D * ((split ? 3.0 : 2.0) * a.Lq + (split ? 3.0 : 2.0) * a.Lk);
+    const double bytes = 2.0 * (double)a.B * a.H * a.D * ((split ? 3.0 : 2.0) * a.Lq + (full ? 4.0 : split ? 3.0 : 2.0) * a.Lk);
     TimingScope ts(OMGSR_TK_ATTN, flops, bytes, st, (long long)a.B * a.H * a.Lq, a.Lk, a.D);
-    if (ts.active) ts.rec.variant = 20;
+    if (ts.active) ts.rec.variant = full ? 23 : 20;
+    if (full) return launch_vae_attn<64, true, true>(a, st, defer);
     return split ? launch_vae_attn<128, true>(a, st, defer) : launch_vae_attn<256, false>(a, st, defer);
 }
 }  // namespace omgsr

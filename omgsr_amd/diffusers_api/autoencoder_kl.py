@@ -9,7 +9,8 @@ Data layout: NCHW tensors at the API boundary (as diffusers), bf16 NHWC inside. 
 as a statistics pass + an apply pass feeding the implicit-GEMM conv; nearest-2x upsampling and the
 encoder's asymmetric pad are folded into the conv's gather; the d=512 single-head mid attention
 uses the batched-GEMM + masked row-softmax path up to 16384 tokens and the fused head_dim-512 kernel
-(ops.attention) past that, or wherever `VaeAttention.fused` / OMGSR_VAE_ATTN_FUSED asks for it.
+(ops.attention) past that, or wherever `VaeAttention.fused` / OMGSR_VAE_ATTN_FUSED asks for it. The range-fallback tier keeps the
+materialised chain unless `VaeAttention.fused_range_fallback` / OMGSR_VAE_ATTN_FUSED_RF opts into the fused full-split kernel.
 """
 from __future__ import annotations
 
@@ -115,19 +116,29 @@ def _parse_fused_knob(value: Optional[str]) -> Optional[bool]:
 
 
 _ENV_FUSED = _parse_fused_knob(os.environ.get("OMGSR_VAE_ATTN_FUSED"))        # read once, at import (A/B runs)
+# OMGSR_VAE_ATTN_FUSED_RF: "1" stands in for a VaeAttention.fused_range_fallback left False; anything else changes nothing
+_ENV_FUSED_RF = _parse_fused_knob(os.environ.get("OMGSR_VAE_ATTN_FUSED_RF")) is True
 
 
-def vae_attention_route(L: int, precise: bool, attn_split: bool, switch: Optional[bool], env: Optional[bool] = None) -> str:
-    """"fused" | "materialised" for a VAE mid-block attention over L tokens. `switch` is the module's tri-state (VaeAttention.fused); when it
-    is None the environment knob `env` stands in. First match wins:
-      range-fallback tier (precise and attn_split)  materialised (it needs split P and split V^T), ValueError past 16384 keys
+def vae_attention_route(L: int, precise: bool, attn_split: bool, switch: Optional[bool], env: Optional[bool] = None, *,
+                        rf_fused: bool = False) -> str:
+    """"fused" | "fused_split" | "materialised" for a VAE mid-block attention over L tokens. `switch` is the module's tri-state
+    (VaeAttention.fused); when it is None the environment knob `env` stands in. `rf_fused`: the range-fallback tier's opt-in
+    (VaeAttention.fused_range_fallback or its knob). First match wins:
+      range-fallback tier (precise and attn_split)  with rf_fused: fused_split (every operand a two-term split, one launch, any L); else
+                                                    materialised (`switch` never applies: the fused kernel it selects has no split P
+                                                    and no split V^T), ValueError past 16384 keys
       switch off                                    materialised (past 16384 keys the softmax kernel refuses the row)
       switch on                                     fused
       unset                                         materialised up to 16384 keys (unchanged default), fused past them"""
     if precise and attn_split:
+        if rf_fused:
+            return "fused_split"
         if L > MATERIALISED_MAX_KEYS:
             raise ValueError(f"the range-fallback VAE attention is limited to {MATERIALISED_MAX_KEYS} keys (got {L}): its split probabilities "
-                             "and split V^T run on the materialised path only; tile the VAE or use the accurate tier's fp16 operands")
+                             "and split V^T run on the materialised path only; tile the VAE or use the accurate tier's fp16 operands, or opt "
+                             "into the fused full-split kernel (AutoencoderKL.set_range_fallback_fused_attention(True) / "
+                             "OMGSR_VAE_ATTN_FUSED_RF=1)")
         return "materialised"
     if switch is None:
         switch = env
@@ -141,6 +152,7 @@ class VaeAttention(nn.Module):
     residual connection."""
 
     fused: Optional[bool] = None        # None: automatic (vae_attention_route); True / False: force the fused / materialised path
+    fused_range_fallback: bool = False  # range-fallback tier only: True = the fused full-split kernel (any L) instead of the materialised chain
 
     def __init__(self, channels: int, groups: int):
         super().__init__()
@@ -181,9 +193,15 @@ class VaeAttention(nn.Module):
         # tier with single bf16 P / V here after the UNet's flash kernel had been fixed)
         full = ops.attn_split()
         qk2 = ops.precise() and (getattr(self, "qk_split", False) or full)
-        route = vae_attention_route(L, ops.precise(), full, self.fused, _ENV_FUSED)
+        route = vae_attention_route(L, ops.precise(), full, self.fused, _ENV_FUSED, rf_fused=self.fused_range_fallback or _ENV_FUSED_RF)
         q = self.to_q.nhwc(g, out_dtype=ops.OUT_BF16, out_split=2 if qk2 else 1)
         k = self.to_k.nhwc(g, out_dtype=ops.OUT_BF16, out_split=2 if qk2 else 1)
+        if route == "fused_split":
+            # one launch of vae_attn_full_kernel on the materialised branch's operands: no scores, probabilities or concatenated V^T in HBM
+            vts = ops.transpose_split(self.to_v.nhwc(g, out_dtype=ops.OUT_F32), ops._round_up(L, 8))      # [N, 2C, ld]: V^T hi rows, then lo rows
+            o = ops.attention(q, k, vts, self.heads, Cc, self.scale, out_split=self.to_out[0].in_split(), q_lo_col=Cc, k_lo_col=Cc, p_split=True)
+            out = self.to_out[0].nhwc(o, residual=x.reshape(N, L, Cc), gn_groups=self.group_norm.num_groups)
+            return ops.carry_gn(out, out.reshape(N, H, W, Cc))
         if route == "fused":
             # one launch of vae_attn_kernel: q (| q_lo) and k (| k_lo) as their projections wrote them, no scores or probabilities in HBM
             vt = ops.linear_t(g, self.to_v.packed(), L)                           # [N, C, round_up(L, 8)]
@@ -406,6 +424,18 @@ class AutoencoderKL(ModelMixin):
                 m.fused = mode
         from .. import precision
         precision._touch()              # captured hipGraphs are keyed on the policy epoch (pipelines/graphed.py): never a stale replay
+
+    def set_range_fallback_fused_attention(self, on: bool) -> None:
+        """The mid-block attentions in the range-fallback tier: True = the fused full-split head_dim-512 kernel (one launch, no 16384-token
+        limit, no score / probability tensors), False = the materialised chain (the default). Other tiers ignore it
+        (VaeAttention.fused_range_fallback)."""
+        if not isinstance(on, bool):
+            raise ValueError("set_range_fallback_fused_attention: on is True or False")
+        for m in self.modules():
+            if isinstance(m, VaeAttention):
+                m.fused_range_fallback = on
+        from .. import precision
+        precision._touch()              # as set_fused_attention: never a stale graph replay
 
     # ---- fast NHWC entry points used by the pipelines -------------------------------------
     def encode_moments_nhwc(self, x_nhwc8: torch.Tensor) -> torch.Tensor:

@@ -1492,7 +1492,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, he
               o_col: int = 0, out_split: int = 1, o_lo_col: Optional[int] = None, q_lo_col: Optional[int] = None,
               k_lo_col: Optional[int] = None, p_split: bool = True) -> torch.Tensor:
     """q [B, Lq, *] (heads at columns q_col + h*D), k [Bk, Lk, *], vt [Bk, heads*D, ld] -> o [B, Lq, heads*D]
-    head_dim 512 (the VAE mid block, any Lk): out_split 1 or 2, q_lo_col / k_lo_col with p_split=False, a single V^T.
+    head_dim 512 (the VAE mid block, any Lk): out_split 1 or 2; q_lo_col / k_lo_col with p_split=False and a single V^T, or (the
+    range-fallback tier: every operand a two-term split) with p_split=True and the split V^T of transpose_split.
     q_lo_col / k_lo_col (both or neither, head_dim 64 or 512): q and k are two-term splits whose low halves start at those columns of the same rows
     (a projection written with out_split = 2); the scores then run three MFMA passes and, with p_split, the probabilities two (attn_split()).
     (an operand for the output projection; out_split 2: [B, Lq, 2*heads*D] as the two-term split; 3: the same bytes per row in the
@@ -1507,13 +1508,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, he
         if out_split != 1 or q_lo_col is not None or k_lo_col is not None:
             raise ValueError("attention: MXFP8 operands take a plain bf16 output and no two-term splits")
         return _attention_mxfp8(q, k, vt, heads, head_dim, scale, q_col, k_col, Lk, out, o_col)
-    if head_dim == 512:             # vae_attn_kernel (ABI v20): checked here, before the library is called
+    if head_dim == 512:             # vae_attn_kernel / vae_attn_full_kernel: checked here, before the library is called
         if out_split == 3:
             raise ValueError("attention: head_dim 512 writes a plain or two-term-split output (out_split 1 or 2), not the MX form")
+        qk2 = q_lo_col is not None and k_lo_col is not None
         if vt.shape[1] == 2 * heads * head_dim:
-            raise ValueError("attention: head_dim 512 takes a single V^T; the two-term-split V^T is limited to head_dim 64")
-        if q_lo_col is not None and k_lo_col is not None and p_split:
-            raise ValueError("attention: head_dim 512 takes split q / k with p_split=False; split probabilities are limited to head_dim 64")
+            if not qk2:
+                raise ValueError("attention: a split V^T comes with split q / k")
+            if not p_split:
+                raise ValueError("attention: head_dim 512 with p_split=False takes a single V^T; the two-term-split V^T comes with p_split=True")
+        elif qk2 and p_split:
+            raise ValueError("attention: head_dim 512 takes split q / k and a single V^T with p_split=False; split probabilities come with "
+                             "the two-term-split V^T")
     _req(q, act_dtype(), "q"); _req(k, act_dtype(), "k"); _req(vt, act_dtype(), "vt")
     B, Lq = q.shape[0], q.shape[1]
     Bk = k.shape[0]
