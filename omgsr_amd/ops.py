@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -234,13 +234,15 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-def _igemm(a: "IgemmArgs", device, what: str, z_batched_api: bool = False) -> None:
+def _igemm(a: "IgemmArgs", device, what: str, z_batched_api: bool = False, workspace: bool = True) -> None:
     """Launch omgsr_igemm; when the library wants to split K (small-M / long-K problems) hand it an fp32 scratch.
-    z_batched_api: the caller is one of the entry points that put the images of a call on grid.z (linear_into / linear_rows / bmm_nt).
-    The library cannot split K there when there is more than one image, so in batch-invariant mode it must not split the one-image
-    call either (round 4: OMGSR-F batch 1 == batch N bit for bit under ops.set_batch_invariant)."""
+    z_batched_api: the caller puts the images of a call on grid.z and offers a workspace (linear_into is the one that does). The library
+    cannot split K there when there is more than one image, so in batch-invariant mode it must not split the one-image call either
+    (round 4: OMGSR-F batch 1 == batch N bit for bit under ops.set_batch_invariant).
+    workspace=False: no query and a NULL workspace, so the library never splits K (linear_rows, linear_t_into, linear_t, bmm_nt and the
+    fp8 form of linear)."""
     lib = _lib.load()
-    need = 0 if (z_batched_api and _BATCH_INVARIANT) else lib.omgsr_igemm_workspace_bytes(C.byref(a))
+    need = 0 if (not workspace or (z_batched_api and _BATCH_INVARIANT)) else lib.omgsr_igemm_workspace_bytes(C.byref(a))
     ws = None
     if need > 0:
         ws = torch.empty(need // 4, device=device, dtype=torch.float32)
@@ -513,6 +515,12 @@ class Mxfp8:
         return Mxfp8(self.codes.reshape(*lead, self.codes.shape[-1]), self.scales.reshape(*lead, self.scales.shape[-1]))
 
 
+def _mxfp8_like(x: torch.Tensor) -> Mxfp8:
+    """An uninitialised Mxfp8 of x's shape."""
+    return Mxfp8(torch.empty(x.shape, device=x.device, dtype=torch.uint8),
+                 torch.empty((*x.shape[:-1], x.shape[-1] // 32), device=x.device, dtype=torch.uint8))
+
+
 def quantize_mxfp8(x: torch.Tensor, out: Optional[Mxfp8] = None) -> Mxfp8:
     """x bf16 or fp32 [..., K] (K % 128 == 0) -> its OMGSR_EL_MXFP8 form, on the device (omgsr_quantize_mxfp8): scale = max(0, biased
     exponent of the block's largest |v| - 8), code = (v / 2^(scale - 127)).clamp(-448, 448) in e4m3fn, round to nearest even.
@@ -527,13 +535,12 @@ def quantize_mxfp8(x: torch.Tensor, out: Optional[Mxfp8] = None) -> Mxfp8:
     if out is not None:
         if out.codes.shape != x.shape or out.scales.shape != (*x.shape[:-1], K // 32) or not (out.codes.is_contiguous() and out.scales.is_contiguous()):
             raise ValueError("quantize_mxfp8: `out` does not match x")
-        codes, scales = out.codes, out.scales
+        out = Mxfp8(out.codes, out.scales)
     else:
-        codes = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-        scales = torch.empty((*x.shape[:-1], K // 32), device=x.device, dtype=torch.uint8)
-    check(_lib.load().omgsr_quantize_mxfp8(x.data_ptr(), EL_F32 if x.dtype == torch.float32 else EL_16, rows, K, K, codes.data_ptr(),
-                                           scales.data_ptr(), _stream()), "omgsr_quantize_mxfp8")
-    return Mxfp8(codes, scales)
+        out = _mxfp8_like(x)
+    check(_lib.load().omgsr_quantize_mxfp8(x.data_ptr(), EL_F32 if x.dtype == torch.float32 else EL_16, rows, K, K, out.codes.data_ptr(),
+                                           out.scales.data_ptr(), _stream()), "omgsr_quantize_mxfp8")
+    return out
 
 
 def pack_linear_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> PackedWeight:
@@ -564,11 +571,12 @@ def _fp8_operand(x, pw: PackedWeight, what: str) -> Optional[Mxfp8]:
 
 
 def _fill_mxfp8(a: IgemmArgs, codes_ptr: int, scales_ptr: int, pw: PackedWeight) -> None:
+    """Operand and weight side of a GEMM over an MXFP8 operand and an fp8-packed linear weight (pack_linear_weight_mxfp8)."""
     a.in_, a.in_scale = codes_ptr, scales_ptr
     a.weight, a.w_scale, a.bias = pw.w.data_ptr(), pw.w_scale.data_ptr(), _ptr(pw.bias)
     a.mxf8 = 1
     a.Cin, a.Cout, a.Cout_pad, a.K_pad = pw.cin, pw.cout, pw.cout_pad, pw.k_pad
-    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
+    _fill_taps_1x1(a)
 
 
 def pack_conv_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> PackedWeight:
@@ -625,9 +633,14 @@ def _out_tensor(shape, cout: int, out_dtype: int, out_split: int, device) -> tor
     return torch.empty((*shape, cout * min(out_split, 2)), device=device, dtype=_ACT)       # split 3 (MX): 4 bytes per channel, like split 2
 
 
-def _fill_k(a: IgemmArgs, pw: PackedWeight) -> None:
-    """Contraction geometry of a packed weight: Cin = every K segment of a tap, in_ld = the operand row it wraps over."""
-    a.Cin = pw.cin
+# The fillers below write one concern each into a ZEROED omgsr_igemm_args (a fresh IgemmArgs()): what they do not mention stays 0 / NULL.
+
+def _fill_weight(a: IgemmArgs, pw: PackedWeight, x_ptr: int, scales_ptr: Optional[int] = None) -> None:
+    """Operand pointer and weight side of a packed weight: pointers, padded extents and the contraction geometry (Cin = every K segment
+    of a tap, in_ld = the operand row it wraps over).
+    scales_ptr: the operand is MXFP8 (x_ptr its codes) and `pw` an fp8-packed linear weight - _fill_mxfp8 on top."""
+    a.in_, a.weight, a.bias, a.weight_cm = x_ptr, pw.w.data_ptr(), _ptr(pw.bias), _ptr(pw.w_cm)
+    a.Cin, a.Cout, a.Cout_pad, a.K_pad = pw.cin, pw.cout, pw.cout_pad, pw.k_pad
     a.overflow_flag = _ovf(pw.w.device)
     a.in_ld = pw.row_channels if pw.row_channels != pw.cin else 0
     a.in_split = int(pw.split >= 2)            # split 3 (MX): 2C slots per tap for C logical channels, like the two-term split
@@ -635,16 +648,40 @@ def _fill_k(a: IgemmArgs, pw: PackedWeight) -> None:
     if pw.mx is not None:
         a.mx_chunks16, a.mx_scale_w1, a.mx_scale_a1, a.mx_scale_w2, a.mx_scale_a2 = pw.mx
         a.mx_fmt = pw.mx_fmt
+    if scales_ptr is not None:
+        _fill_mxfp8(a, x_ptr, scales_ptr, pw)
+
+
+def _fill_taps_1x1(a: IgemmArgs) -> None:
+    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
+
+
+def _fill_gemm(a: IgemmArgs, M: int, batch: int = 1, in_bstride: int = 0, w_bstride: int = 0, out_bstride: int = 0) -> None:
+    """GEMM-shaped geometry: M rows as a 1 x M map under a 1x1 kernel; `batch` problems on grid.z, the three strides in elements."""
+    a.N, a.H, a.W, a.Ho, a.Wo = 1, 1, M, 1, M
+    _fill_taps_1x1(a)
+    a.batch, a.in_bstride, a.w_bstride, a.out_bstride = batch, in_bstride, w_bstride, out_bstride
 
 
 def _fill_out(a: IgemmArgs, out: torch.Tensor, out_split: int, residual: Optional[torch.Tensor], cout: int) -> None:
+    """A dense output (out_split 2: [hi | lo] at the front of rows that may be wider) and the residual."""
     a.out = out.data_ptr()
     a.out_dtype = OUT_F32 if out.dtype == torch.float32 else OUT_BF16
     a.out_lo_off = cout if out_split == 2 else 0
+    a.out_ld = out.shape[-1] if out_split == 2 else 0
     a.out_mx = {3: 1, 4: 6}.get(out_split, 0)
     if residual is not None:
-        a.residual = residual.data_ptr()
-        a.res_el = _el(residual, "residual")
+        a.residual, a.res_el = residual.data_ptr(), _el(residual, "residual")
+
+
+def _fill_out_slice(a: IgemmArgs, buf: torch.Tensor, first: int, *, ld: int = 0, lo_off: int = 0, t_rows: Optional[int] = None) -> None:
+    """A 16-bit output inside a caller's buffer, `first` elements in. Row-major window (linear_into): rows of pitch `ld`, the low halves of
+    a two-term split `lo_off` columns behind the high ones. t_rows given: the transposed layout (LAYOUT_T), t_rows rows per image, pitch
+    buf.shape[-1]."""
+    a.out, a.out_dtype = buf.data_ptr() + 2 * first, OUT_BF16
+    a.out_ld, a.out_lo_off = ld, lo_off
+    if t_rows is not None:
+        a.out_layout, a.t_rows, a.t_ld = LAYOUT_T, t_rows, buf.shape[-1]
 
 
 def _conv_args(a: IgemmArgs, x: torch.Tensor, pw: PackedWeight, stride, pad, upsample, act, residual, gate, out_dtype, alpha, out, out_split,
@@ -668,22 +705,35 @@ def _conv_args(a: IgemmArgs, x: torch.Tensor, pw: PackedWeight, stride, pad, ups
         out = _out_tensor((N, Ho, Wo), pw.cout, out_dtype, out_split, x.device)
     if residual is not None and tuple(residual.shape) != (N, Ho, Wo, pw.cout):
         raise ValueError(f"residual shape {tuple(residual.shape)} != output {(N, Ho, Wo, pw.cout)}")
-    a.in_, a.weight, a.bias, a.gate = x.data_ptr(), pw.w.data_ptr(), _ptr(pw.bias), _ptr(gate)
-    _fill_out(a, out, out_split, residual, pw.cout)
-    a.weight_cm = _ptr(pw.w_cm)
+    _fill_weight(a, pw, x.data_ptr())
     a.weight_ph = _ptr(pw.w_ph) if upsample else None
-    a.N, a.H, a.W = N, H, W
-    _fill_k(a, pw)
-    a.Cout, a.Cout_pad, a.K_pad = pw.cout, pw.cout_pad, pw.k_pad
+    a.N, a.H, a.W, a.Ho, a.Wo = N, H, W, Ho, Wo
     a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = pw.R, pw.S, stride, pt, pl, int(upsample)
-    a.Ho, a.Wo = Ho, Wo
-    a.act, a.out_layout = act, LAYOUT_NHWC
-    a.t_rows, a.t_ld = 0, 0
-    a.out_ld = out.shape[-1] if out_split == 2 else 0
-    a.batch, a.in_bstride, a.w_bstride, a.out_bstride = 1, 0, 0, 0
-    a.alpha = alpha
+    _fill_out(a, out, out_split, residual, pw.cout)
+    a.gate, a.act, a.alpha, a.batch = _ptr(gate), act, alpha, 1
     a.sample_rows = sample_rows or Ho * Wo
     return x, out
+
+
+class GnHandle(NamedTuple):
+    """The GroupNorm statistics a producer's epilogue left, carried by its output as `_omgsr_gn` (read by index: a plain tuple serves too)."""
+    partial: torch.Tensor      # [N, nslot, entries, 2] (sum, sum of squares); entries = groups, or channels for odd group sizes
+    groups: int                # the group count the producer was told
+    ptr: int                   # the output's data_ptr() and _version when the statistics were left: stale once either moves
+    version: int
+
+
+def _leave_gn(out: torch.Tensor, partial: torch.Tensor, groups: int) -> None:
+    """Attach the handle group_norm_stats(out) / group_norm_pair consume."""
+    out._omgsr_gn = GnHandle(partial, groups, out.data_ptr(), out._version)
+
+
+def _gn_handle(x: torch.Tensor, N: int):
+    """x's handle when it still describes x (same storage, not written since) for N images, else None."""
+    h = getattr(x, "_omgsr_gn", None)
+    if h is not None and h[2] == x.data_ptr() and h[3] == x._version and h[0].shape[0] == N:
+        return h
+    return None
 
 
 def _conv_gn(a: IgemmArgs, gn_groups: int, out_split: int, device):
@@ -785,7 +835,7 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: tuple[int
     _igemm(a, x.device, "omgsr_igemm(conv2d)")
     del keep
     if partial is not None:
-        out._omgsr_gn = (partial, gn_groups, out.data_ptr(), out._version)      # consumed by group_norm_stats(out)
+        _leave_gn(out, partial, gn_groups)
     return out
 
 
@@ -794,13 +844,25 @@ def _conv2d_mxfp8(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight, out: torch.Tenso
     if xq.codes.shape[-1] != pw8.cin or a.Cout != pw8.cout:
         raise ValueError(f"conv2d_mxfp8: operand K {xq.codes.shape[-1]} / Cout {a.Cout} do not match the packed weight ({pw8.cin}, {pw8.cout})")
     a.in_, a.in_scale = xq.codes.data_ptr(), xq.scales.data_ptr()
-    a.weight, a.weight_cm, a.w_scale, a.weight_ph = pw8.w_cm.data_ptr(), pw8.w_cm.data_ptr(), pw8.w_scale.data_ptr(), None
-    a.Cout_pad, a.K_pad = pw8.w_cm.shape[2], 9 * pw8.cin
-    a.bias = _ptr(pw8.bias) if a.bias is None else a.bias
+    _fill_conv_mxfp8(a, pw8)
     partial = _conv_gn(a, gn_groups, 1, out.device)
     check(_lib.load().omgsr_conv_mxfp8(C.byref(a), _stream()), "omgsr_conv_mxfp8")
     if partial is not None:
-        out._omgsr_gn = (partial, gn_groups, out.data_ptr(), out._version)
+        _leave_gn(out, partial, gn_groups)
+    return out
+
+
+def _conv_mxfp8_args(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight, act: int, residual, out_dtype: int, sample_rows: int) -> torch.Tensor:
+    """Geometry, epilogue and output of one 3x3 stride-1 pad-1 MXFP8 conv problem (the operand and weight side: _conv2d_mxfp8(_multi));
+    returns the output it allocated."""
+    N, H, W, Cin = xq.codes.shape
+    out = _out_tensor((N, H, W), pw8.cout, out_dtype, 1, xq.codes.device)
+    if residual is not None and tuple(residual.shape) != (N, H, W, pw8.cout):
+        raise ValueError(f"residual shape {tuple(residual.shape)} != output {(N, H, W, pw8.cout)}")
+    _fill_out(a, out, 1, residual, pw8.cout)
+    a.N, a.H, a.W, a.Ho, a.Wo, a.Cin, a.Cout = N, H, W, H, W, Cin, pw8.cout
+    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 3, 3, 1, 1, 1, 0
+    a.act, a.batch, a.alpha, a.sample_rows = act, 1, 1.0, sample_rows or H * W
     return out
 
 
@@ -810,19 +872,9 @@ def conv2d_mxfp8(xq: "Mxfp8", pw8: PackedWeight, *, act: int = ACT_NONE, residua
     weight -> [N,H,W,Cout8]. No other kernel stands behind it: a problem omgsr_conv_mxfp8_ok does not accept raises (OMGSR_E_SHAPE)."""
     if not isinstance(xq, Mxfp8) or not pw8.fp8 or pw8.w_cm is None:
         raise ValueError("conv2d_mxfp8: an Mxfp8 operand and a pack_conv_weight_mxfp8 weight")
-    N, H, W, Cin = xq.codes.shape
     a = IgemmArgs()
-    out = _out_tensor((N, H, W), pw8.cout, out_dtype, 1, xq.codes.device)
-    if residual is not None and tuple(residual.shape) != (N, H, W, pw8.cout):
-        raise ValueError(f"residual shape {tuple(residual.shape)} != output {(N, H, W, pw8.cout)}")
+    out = _conv_mxfp8_args(a, xq, pw8, act, residual, out_dtype, sample_rows)
     a.gate = _ptr(gate)
-    _fill_out(a, out, 1, residual, pw8.cout)
-    a.N, a.H, a.W, a.Cin, a.Cout = N, H, W, Cin, pw8.cout
-    a.Cout_pad, a.K_pad = pw8.w_cm.shape[2], 9 * pw8.cin
-    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 3, 3, 1, 1, 1, 0
-    a.Ho, a.Wo, a.act, a.out_layout = H, W, act, LAYOUT_NHWC
-    a.batch, a.alpha, a.sample_rows = 1, 1.0, sample_rows or H * W
-    a.overflow_flag = None
     return _conv2d_mxfp8(a, xq, pw8, out, gn_groups)
 
 
@@ -857,7 +909,7 @@ def _conv2d_mxfp8_multi(arr, n: int, xqs, pw8: PackedWeight, outs, gn_groups: in
     check(_lib.load().omgsr_conv_mxfp8_multi(arr, n, _stream()), "omgsr_conv_mxfp8_multi")
     for out, partial in zip(outs, partials):
         if partial is not None:
-            out._omgsr_gn = (partial, gn_groups, out.data_ptr(), out._version)
+            _leave_gn(out, partial, gn_groups)
     return outs
 
 
@@ -873,19 +925,7 @@ def conv2d_mxfp8_multi(xqs, pw8: PackedWeight, *, act: int = ACT_NONE, residuals
     arr = (IgemmArgs * n)()
     outs = []
     for i, xq in enumerate(xqs):
-        N, H, W, Cin = xq.codes.shape
-        a = arr[i]
-        out = _out_tensor((N, H, W), pw8.cout, out_dtype, 1, xq.codes.device)
-        residual = None if residuals is None else residuals[i]
-        if residual is not None and tuple(residual.shape) != (N, H, W, pw8.cout):
-            raise ValueError(f"residual shape {tuple(residual.shape)} != output {(N, H, W, pw8.cout)}")
-        _fill_out(a, out, 1, residual, pw8.cout)
-        a.N, a.H, a.W, a.Cin, a.Cout = N, H, W, Cin, pw8.cout
-        a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 3, 3, 1, 1, 1, 0
-        a.Ho, a.Wo, a.act, a.out_layout = H, W, act, LAYOUT_NHWC
-        a.batch, a.alpha, a.sample_rows = 1, 1.0, H * W
-        a.overflow_flag = None
-        outs.append(out)
+        outs.append(_conv_mxfp8_args(arr[i], xq, pw8, act, None if residuals is None else residuals[i], out_dtype, 0))
     return _conv2d_mxfp8_multi(arr, n, xqs, pw8, outs, gn_groups)
 
 
@@ -944,7 +984,7 @@ def conv2d_multi(xs, pw: PackedWeight, *, stride: int = 1, pad: tuple[int, int, 
     check(lib.omgsr_igemm_multi(arr, n, _stream()), "omgsr_igemm_multi(conv2d_multi)")
     for out, partial in zip(outs, partials):
         if partial is not None:
-            out._omgsr_gn = (partial, gn_groups, out.data_ptr(), out._version)
+            _leave_gn(out, partial, gn_groups)
     return outs
 
 
@@ -964,13 +1004,11 @@ def linear(x: torch.Tensor, pw: PackedWeight, *, act: int = ACT_NONE, residual: 
         if residual is not None and residual.numel() != M * pw.cout:
             raise ValueError("linear: residual must be [..., Cout]")
         a = IgemmArgs()
-        _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)
-        a.gate = _ptr(gate)
+        _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)       # (not _fill_weight: this form never took the contraction-geometry fields)
+        _fill_gemm(a, M)
         _fill_out(a, out, 1, residual, pw.cout)
-        a.N, a.H, a.W, a.Ho, a.Wo = 1, 1, M, 1, M
-        a.act, a.out_layout, a.batch, a.alpha = act, LAYOUT_NHWC, 1, alpha
-        a.sample_rows = M
-        check(_lib.load().omgsr_igemm(C.byref(a), _stream()), "omgsr_igemm(linear, mxfp8)")
+        a.gate, a.act, a.alpha, a.sample_rows = _ptr(gate), act, alpha, M
+        _igemm(a, out.device, "omgsr_igemm(linear, mxfp8)", workspace=False)
         return out
     lead = x.shape[:-1]
     M = 1
@@ -1019,28 +1057,19 @@ def linear_into(x: torch.Tensor, pw: PackedWeight, out: torch.Tensor, row0: int,
         raise ValueError("linear_into: slice does not fit")
     if residual is not None and (Bz != 1 or residual.numel() != M * pw.cout):
         raise ValueError("linear_into: residual must be a dense [M, Cout] (unbatched call)")
-    a = IgemmArgs()
-    a.in_, a.weight, a.bias, a.gate = x.data_ptr(), pw.w.data_ptr(), _ptr(pw.bias), _ptr(gate)
-    a.out = out.data_ptr() + 2 * (row0 * ld + col0)
-    a.out_dtype = OUT_BF16
+    lo_off = 0
     if out_split == 2:
-        a.out_lo_off = (lo_col0 - col0) if lo_col0 is not None else pw.cout
-        if a.out_lo_off < pw.cout or col0 + a.out_lo_off + pw.cout > ld:
+        lo_off = (lo_col0 - col0) if lo_col0 is not None else pw.cout
+        if lo_off < pw.cout or col0 + lo_off + pw.cout > ld:
             raise ValueError("linear_into: the low halves do not fit the row")
+    a = IgemmArgs()
+    _fill_weight(a, pw, x.data_ptr(), None if xq is None else xq.scales.data_ptr())
+    _fill_gemm(a, M, Bz, M * K, 0, nrows * ld)
+    _fill_out_slice(a, out, row0 * ld + col0, ld=ld, lo_off=lo_off)
     if residual is not None:
         a.residual, a.res_el = residual.data_ptr(), _el(residual, "residual")
-    a.N, a.H, a.W = 1, 1, M
-    _fill_k(a, pw)
-    a.Cout, a.Cout_pad, a.K_pad = pw.cout, pw.cout_pad, pw.k_pad
-    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
-    a.Ho, a.Wo = 1, M
-    a.act, a.out_layout = act, LAYOUT_NHWC
-    a.out_ld = ld
-    a.batch, a.alpha = Bz, 1.0
-    a.in_bstride, a.w_bstride, a.out_bstride = M * K, 0, nrows * ld
+    a.gate, a.act, a.alpha = _ptr(gate), act, 1.0
     a.sample_rows = sample_rows or M              # rows of ONE image when the caller flattened a batch into M (batch-invariant dispatch)
-    if xq is not None:
-        _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)
     _igemm(a, x.device, "omgsr_igemm(linear_into)", z_batched_api=True)
 
 
@@ -1061,20 +1090,14 @@ def linear_rows(x_buf: torch.Tensor, row0: int, rows: int, pw: PackedWeight, *, 
     if residual is not None and tuple(residual.shape) != (B, rows, pw.cout):
         raise ValueError("linear_rows: residual must be [B, rows, Cout]")
     a = IgemmArgs()
-    a.in_, a.weight, a.bias, a.gate = x_buf.data_ptr() + 2 * row0 * K, pw.w.data_ptr(), _ptr(pw.bias), _ptr(gate)
+    if xq is None:
+        _fill_weight(a, pw, x_buf.data_ptr() + 2 * row0 * K)
+    else:                                         # one byte per code, one scale per 32 of them
+        _fill_weight(a, pw, x_buf.data_ptr() + row0 * K, xq.scales.data_ptr() + row0 * (K // 32))
+    _fill_gemm(a, rows, B, L * K, 0, rows * pw.cout)
     _fill_out(a, out, 1, residual, pw.cout)
-    a.N, a.H, a.W = 1, 1, rows
-    _fill_k(a, pw)
-    a.Cout, a.Cout_pad, a.K_pad = pw.cout, pw.cout_pad, pw.k_pad
-    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
-    a.Ho, a.Wo = 1, rows
-    a.act, a.out_layout = act, LAYOUT_NHWC
-    a.batch, a.alpha = B, 1.0
-    a.in_bstride, a.w_bstride, a.out_bstride = L * K, 0, rows * pw.cout
-    a.sample_rows = rows
-    if xq is not None:
-        _fill_mxfp8(a, x_buf.data_ptr() + row0 * K, xq.scales.data_ptr() + row0 * (K // 32), pw)
-    check(_lib.load().omgsr_igemm(C.byref(a), _stream()), "omgsr_igemm(linear_rows)")
+    a.gate, a.act, a.alpha, a.sample_rows = _ptr(gate), act, 1.0, rows
+    _igemm(a, x_buf.device, "omgsr_igemm(linear_rows)", workspace=False)
     return out
 
 
@@ -1095,20 +1118,11 @@ def linear_t_into(x: torch.Tensor, pw: PackedWeight, out_t: torch.Tensor, key0: 
     if out_t.dim() not in (2, 3) or out_t.shape[-2] != pw.cout or key0 + L > out_t.shape[-1] or K != pw.row_channels:
         raise ValueError("linear_t_into: slice does not fit")
     a = IgemmArgs()
-    a.in_, a.weight, a.bias, a.out = x.data_ptr(), pw.w.data_ptr(), _ptr(pw.bias), out_t.data_ptr() + 2 * key0
-    a.N, a.H, a.W = 1, 1, L
-    _fill_k(a, pw)
-    a.Cout, a.Cout_pad, a.K_pad = pw.cout, pw.cout_pad, pw.k_pad
-    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
-    a.Ho, a.Wo = 1, L
-    a.act, a.out_dtype, a.out_layout = ACT_NONE, OUT_BF16, LAYOUT_T
-    a.t_rows, a.t_ld = L, out_t.shape[-1]
-    a.batch, a.alpha = Bz, 1.0
-    a.in_bstride, a.w_bstride, a.out_bstride = L * K, 0, pw.cout * out_t.shape[-1]
-    a.sample_rows = L
-    if xq is not None:
-        _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)
-    check(_lib.load().omgsr_igemm(C.byref(a), _stream()), "omgsr_igemm(linear_t_into)")
+    _fill_weight(a, pw, x.data_ptr(), None if xq is None else xq.scales.data_ptr())
+    _fill_gemm(a, L, Bz, L * K, 0, pw.cout * out_t.shape[-1])
+    _fill_out_slice(a, out_t, key0, t_rows=L)
+    a.alpha, a.sample_rows = 1.0, L
+    _igemm(a, x.device, "omgsr_igemm(linear_t_into)", workspace=False)
 
 
 def linear_t(x: torch.Tensor, pw: PackedWeight, rows_per_batch: int, ld: Optional[int] = None) -> torch.Tensor:
@@ -1124,18 +1138,11 @@ def linear_t(x: torch.Tensor, pw: PackedWeight, rows_per_batch: int, ld: Optiona
     out = torch.zeros((B, pw.cout, ld), device=x.device, dtype=act_dtype()) if ld != L else \
         torch.empty((B, pw.cout, ld), device=x.device, dtype=act_dtype())
     a = IgemmArgs()
-    a.in_, a.weight, a.bias, a.gate, a.residual, a.out = x.data_ptr(), pw.w.data_ptr(), _ptr(pw.bias), None, None, out.data_ptr()
-    a.N, a.H, a.W = 1, 1, B * L
-    _fill_k(a, pw)
-    a.Cout, a.Cout_pad, a.K_pad = pw.cout, pw.cout_pad, pw.k_pad
-    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
-    a.Ho, a.Wo = 1, B * L
-    a.act, a.out_dtype, a.out_layout = ACT_NONE, OUT_BF16, LAYOUT_T
-    a.t_rows, a.t_ld = L, ld
-    a.batch, a.in_bstride, a.w_bstride, a.out_bstride = 1, 0, 0, 0
-    a.alpha = 1.0
-    a.sample_rows = L
-    check(_lib.load().omgsr_igemm(C.byref(a), _stream()), "omgsr_igemm(linear_t)")
+    _fill_weight(a, pw, x.data_ptr())
+    _fill_gemm(a, B * L)                          # one problem of B * L rows: the transposed epilogue finds the image from t_rows
+    _fill_out_slice(a, out, 0, t_rows=L)
+    a.alpha, a.sample_rows = 1.0, L
+    _igemm(a, x.device, "omgsr_igemm(linear_t)", workspace=False)
     return out
 
 
@@ -1178,21 +1185,15 @@ def bmm_nt(a_mat: torch.Tensor, b_mat: torch.Tensor, *, alpha: float = 1.0, out_
     split = out_split if out_dtype == OUT_BF16 else 1
     out = torch.empty((B, M, Np * split), device=a_mat.device, dtype=act_dtype() if out_dtype == OUT_BF16 else torch.float32)
     a = IgemmArgs()
-    a.in_, a.weight, a.bias, a.gate, a.residual, a.out = a_mat.data_ptr(), b_mat.data_ptr(), None, None, None, out.data_ptr()
-    a.N, a.H, a.W, a.Cin = 1, 1, M, Kb
-    a.Cout, a.Cout_pad, a.K_pad = Np, Np, Kb
+    a.in_, a.weight = a_mat.data_ptr(), b_mat.data_ptr()          # the second factor stands where a packed weight would: no padding, no bias
+    a.Cin, a.Cout, a.Cout_pad, a.K_pad = Kb, Np, Np, Kb
     if both_split:
         a.in_ld, a.in_split, a.w_split = K, 1, 1
         a.overflow_flag = _ovf(a_mat.device)
-    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 1, 1, 1, 0, 0, 0
-    a.Ho, a.Wo = 1, M
-    a.act, a.out_dtype, a.out_layout = ACT_NONE, out_dtype, LAYOUT_NHWC
-    a.t_rows, a.t_ld = 0, 0
-    a.out_lo_off = Np if split == 2 else 0
-    a.out_ld = Np * split if split == 2 else 0
-    a.batch, a.in_bstride, a.w_bstride, a.out_bstride = B, M * K, Np * Kb, M * Np * split
-    a.alpha = alpha
-    check(_lib.load().omgsr_igemm(C.byref(a), _stream()), "omgsr_igemm(bmm_nt)")
+    _fill_gemm(a, M, B, M * K, Np * Kb, M * Np * split)
+    _fill_out(a, out, 2 if split == 2 else 1, None, Np)
+    a.out_dtype, a.alpha = out_dtype, alpha                       # (out_dtype as the caller gave it, not as _fill_out reads it off the tensor)
+    _igemm(a, a_mat.device, "omgsr_igemm(bmm_nt)", workspace=False)
     return out
 
 
@@ -1212,10 +1213,14 @@ def split_rows_hhl(x: torch.Tensor, pad_rows: int = 0) -> torch.Tensor:
 # K4: GroupNorm
 
 def _fused_gn(x: torch.Tensor, groups: int, N: int):
-    fused = getattr(x, "_omgsr_gn", None)
-    if fused is not None and fused[1] == groups and fused[2] == x.data_ptr() and fused[3] == x._version and fused[0].shape[0] == N:
-        return fused[0]
-    return None
+    h = _gn_handle(x, N)
+    return h[0] if h is not None and h[1] == groups else None
+
+
+def _gn_stats_out(N: int, groups: int, device):
+    """Uninitialised (mean, rstd, var) [N, G] f32."""
+    mean = torch.empty((N, groups), device=device, dtype=torch.float32)
+    return mean, torch.empty_like(mean), torch.empty_like(mean)
 
 
 def group_norm_stats(x: torch.Tensor, groups: int, eps: float):
@@ -1224,9 +1229,7 @@ def group_norm_stats(x: torch.Tensor, groups: int, eps: float):
     N, Cc = x.shape[0], x.shape[-1]
     HW = x.numel() // (N * Cc)
     lib = _lib.load()
-    mean = torch.empty((N, groups), device=x.device, dtype=torch.float32)
-    rstd = torch.empty_like(mean)
-    var = torch.empty_like(mean)
+    mean, rstd, var = _gn_stats_out(N, groups, x.device)
     fused = _fused_gn(x, groups, N)
     if fused is not None:
         # the producing conv already reduced this tensor (omgsr_igemm gn_partial): fold its partials only
@@ -1274,10 +1277,7 @@ def group_norm_stats_merged(tensors, tiles, N: int, groups: int, eps: float):
         a.count[k] = float(t.shape[1] * t.shape[2] * (t.shape[3] // groups))
         a.weight[k] = t.shape[1] * t.shape[2] / tot
     a.ngroups = len(tensors)
-    dev = tensors[0].device
-    mean = torch.empty((N, groups), device=dev, dtype=torch.float32)
-    rstd = torch.empty_like(mean)
-    var = torch.empty_like(mean)
+    mean, rstd, var = _gn_stats_out(N, groups, tensors[0].device)
     check(_lib.load().omgsr_groupnorm_finalize_merged(C.byref(a), mean.data_ptr(), rstd.data_ptr(), var.data_ptr(), N, groups,
                                                       eps, _stream()), "omgsr_groupnorm_finalize_merged")
     return mean, rstd, var
@@ -1305,18 +1305,16 @@ def group_norm_apply_shared(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Ten
                             act: int = ACT_NONE, split: int = 1, also_cast: int = 0):
     """x [T*N, ..., C] tile-major; mean / rstd [N, G]: row r is normalised with the statistics of image r % N.
     also_cast 1 | 2 | 3: returns (y, x as a plain / split / mixed-precision operand) - see group_norm_apply."""
-    xel = _el(x, "x")
-    rows, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (rows * Cc)
-    y = _operand_like(x, split)
-    y2 = _cast_twin(x, xel, also_cast)
-    fused = y2 is not None and y2 is not x
-    check(_lib.load().omgsr_groupnorm_apply_shared(x.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
-                                                   _ptr(beta), rows, HW, Cc, groups, act, mean.shape[0], xel,
-                                                   _el_of_split(split), y2.data_ptr() if fused else None,
-                                                   _el_of_split(also_cast) if also_cast else EL_16, _ovf(x.device) if fused else None, _stream()),
-          "omgsr_groupnorm_apply_shared")
-    return (y, y2) if also_cast else y
+    return _group_norm_apply(x, mean, rstd, gamma, beta, groups, act, False, split, also_cast, shared=True)
+
+
+def _gn_apply_table(xs, ys, y2s, Cc: int):
+    """The omgsr_gn_apply_group table of a multi launch: tensor k reads xs[k] and writes ys[k] (and y2s[k] unless None)."""
+    desc = (_lib.GnApplyGroup * len(xs))()
+    for k, x in enumerate(xs):
+        desc[k].x, desc[k].y, desc[k].y2 = x.data_ptr(), ys[k].data_ptr(), _ptr(y2s[k])
+        desc[k].rows, desc[k].HW = x.shape[0], x.numel() // (x.shape[0] * Cc)
+    return desc
 
 
 def group_norm_apply_multi(xs, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE, split: int = 1,
@@ -1333,10 +1331,7 @@ def group_norm_apply_multi(xs, mean: torch.Tensor, rstd: torch.Tensor, gamma, be
     ys = [_operand_like(x, split) for x in xs]
     y2s = [_cast_twin(x, xel, also_cast) for x in xs]
     fused = bool(also_cast) and xel == EL_F32
-    desc = (_lib.GnApplyGroup * len(xs))()
-    for k, x in enumerate(xs):
-        desc[k].x, desc[k].y, desc[k].y2 = x.data_ptr(), ys[k].data_ptr(), (y2s[k].data_ptr() if fused else None)
-        desc[k].rows, desc[k].HW = x.shape[0], x.numel() // (x.shape[0] * Cc)
+    desc = _gn_apply_table(xs, ys, y2s if fused else [None] * len(xs), Cc)
     check(_lib.load().omgsr_groupnorm_apply_multi(desc, len(xs), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta), Cc, groups, act,
                                                   mean.shape[0], xel, _el_of_split(split), _el_of_split(also_cast) if also_cast else EL_16,
                                                   _ovf(xs[0].device) if fused else None, _stream()),
@@ -1354,17 +1349,24 @@ def group_norm_apply(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, ga
         if also_cast or inplace:
             raise ValueError("group_norm_apply: split 5 (MXFP8) has no second output and cannot run in place")
         return group_norm_apply_mxfp8(x, mean, rstd, gamma, beta, groups, act)
+    return _group_norm_apply(x, mean, rstd, gamma, beta, groups, act, inplace, split, also_cast, shared=False)
+
+
+def _group_norm_apply(x, mean, rstd, gamma, beta, groups: int, act: int, inplace: bool, split: int, also_cast: int, shared: bool):
+    """The body of group_norm_apply (row r uses statistics row r: omgsr_groupnorm_apply) and group_norm_apply_shared (row r uses statistics
+    row r % mean.shape[0]: omgsr_groupnorm_apply_shared, which takes that count behind `act`)."""
     xel = _el(x, "x")
-    N, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (N * Cc)
+    rows, Cc = x.shape[0], x.shape[-1]
+    HW = x.numel() // (rows * Cc)
     y = x if (inplace and xel == EL_16 and split == 1 and not also_cast) else _operand_like(x, split)
     y2 = _cast_twin(x, xel, also_cast)
     fused = y2 is not None and y2 is not x
-    check(_lib.load().omgsr_groupnorm_apply(x.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
-                                            _ptr(beta), N, HW, Cc, groups, act, xel, _el_of_split(split),
-                                            y2.data_ptr() if fused else None, _el_of_split(also_cast) if also_cast else EL_16,
-                                            _ovf(x.device) if fused else None, _stream()),
-          "omgsr_groupnorm_apply")
+    lib = _lib.load()
+    fn, what, nimg = (lib.omgsr_groupnorm_apply_shared, "omgsr_groupnorm_apply_shared", (mean.shape[0],)) if shared else \
+        (lib.omgsr_groupnorm_apply, "omgsr_groupnorm_apply", ())
+    check(fn(x.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta), rows, HW, Cc, groups, act, *nimg, xel,
+             _el_of_split(split), y2.data_ptr() if fused else None, _el_of_split(also_cast) if also_cast else EL_16,
+             _ovf(x.device) if fused else None, _stream()), what)
     return (y, y2) if also_cast else y
 
 
@@ -1377,11 +1379,10 @@ def group_norm_apply_mxfp8(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tens
     HW = x.numel() // (rows * Cc)
     if Cc % 128:
         raise ValueError(f"group_norm_apply_mxfp8: C = {Cc} is not a multiple of 128")
-    codes = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-    scales = torch.empty((*x.shape[:-1], Cc // 32), device=x.device, dtype=torch.uint8)
-    check(_lib.load().omgsr_groupnorm_apply_mxfp8(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
+    out = _mxfp8_like(x)
+    check(_lib.load().omgsr_groupnorm_apply_mxfp8(x.data_ptr(), out.codes.data_ptr(), out.scales.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
                                                   _ptr(beta), rows, HW, Cc, groups, act, mean.shape[0], xel, _stream()), "omgsr_groupnorm_apply_mxfp8")
-    return Mxfp8(codes, scales)
+    return out
 
 
 def group_norm_apply_mxfp8_multi(xs, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE):
@@ -1396,12 +1397,8 @@ def group_norm_apply_mxfp8_multi(xs, mean: torch.Tensor, rstd: torch.Tensor, gam
         raise ValueError("group_norm_apply_mxfp8_multi: one channel count and element kind per launch")
     if Cc % 128:
         raise ValueError(f"group_norm_apply_mxfp8_multi: C = {Cc} is not a multiple of 128")
-    outs = [Mxfp8(torch.empty(x.shape, device=x.device, dtype=torch.uint8),
-                  torch.empty((*x.shape[:-1], Cc // 32), device=x.device, dtype=torch.uint8)) for x in xs]
-    desc = (_lib.GnApplyGroup * len(xs))()
-    for k, x in enumerate(xs):
-        desc[k].x, desc[k].y, desc[k].y2 = x.data_ptr(), outs[k].codes.data_ptr(), outs[k].scales.data_ptr()
-        desc[k].rows, desc[k].HW = x.shape[0], x.numel() // (x.shape[0] * Cc)
+    outs = [_mxfp8_like(x) for x in xs]
+    desc = _gn_apply_table(xs, [o.codes for o in outs], [o.scales for o in outs], Cc)
     check(_lib.load().omgsr_groupnorm_apply_mxfp8_multi(desc, len(xs), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta), Cc, groups, act,
                                                         mean.shape[0], xel, _stream()), "omgsr_groupnorm_apply_mxfp8_multi")
     return outs
@@ -1415,10 +1412,8 @@ def group_norm(x: torch.Tensor, gamma, beta, groups: int, eps: float, act: int =
 def _fused_gn_channels(x: torch.Tensor, N: int):
     """The producer's partials when it left them PER CHANNEL ([N, nslot, C, 2]: they fold into any group boundary, whatever group count
     the producer was told), else None. _fused_gn's validity rules otherwise."""
-    fused = getattr(x, "_omgsr_gn", None)
-    if fused is not None and fused[2] == x.data_ptr() and fused[3] == x._version and fused[0].shape[0] == N and fused[0].shape[2] == x.shape[-1]:
-        return fused[0]
-    return None
+    h = _gn_handle(x, N)
+    return h[0] if h is not None and h[0].shape[2] == x.shape[-1] else None
 
 
 def group_norm_pair_stats(a: torch.Tensor, b: torch.Tensor, groups: int, eps: float):
@@ -1432,9 +1427,7 @@ def group_norm_pair_stats(a: torch.Tensor, b: torch.Tensor, groups: int, eps: fl
     if pa is None or pb is None:
         return None
     HW = a.numel() // (N * Ca)
-    mean = torch.empty((N, groups), device=a.device, dtype=torch.float32)
-    rstd = torch.empty_like(mean)
-    var = torch.empty_like(mean)
+    mean, rstd, var = _gn_stats_out(N, groups, a.device)
     check(_lib.load().omgsr_groupnorm_finalize2(pa.data_ptr(), pa.shape[1], Ca, pb.data_ptr(), pb.shape[1], Cb, mean.data_ptr(), rstd.data_ptr(),
                                                 var.data_ptr(), N, groups, float(HW) * ((Ca + Cb) // groups), eps, _stream()),
           "omgsr_groupnorm_finalize2")
@@ -1522,24 +1515,13 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, he
                              "the two-term-split V^T")
     _req(q, act_dtype(), "q"); _req(k, act_dtype(), "k"); _req(vt, act_dtype(), "vt")
     B, Lq = q.shape[0], q.shape[1]
-    Bk = k.shape[0]
     Lk = Lk if Lk is not None else k.shape[1]
     inner = heads * head_dim
     if out is None:
         out = torch.empty((B, Lq, inner * min(out_split, 2)), device=q.device, dtype=act_dtype())      # split 3 (MX): 4 bytes per channel
     a = AttnArgs()
-    esz = 2
-    a.q = q.data_ptr() + q_col * esz
-    a.k = k.data_ptr() + k_col * esz
-    a.vt = vt.data_ptr()
-    a.o = out.data_ptr() + o_col * esz
-    a.B, a.H, a.D, a.Lq, a.Lk = B, heads, head_dim, Lq, Lk
-    a.q_ld, a.k_ld, a.vt_ld, a.o_ld = q.shape[-1], k.shape[-1], vt.shape[-1], out.shape[-1]
-    a.q_bstride = Lq * q.shape[-1]
-    a.k_bstride = 0 if Bk == 1 and B > 1 else k.shape[1] * k.shape[-1]
-    a.vt_bstride = 0 if Bk == 1 and B > 1 else vt.shape[1] * vt.shape[-1]
-    a.o_bstride = Lq * out.shape[-1]
-    a.scale = scale
+    _fill_attn(a, q, k, vt, out, o_col, heads, head_dim, Lk, scale)
+    a.q, a.k, a.vt = q.data_ptr() + q_col * 2, k.data_ptr() + k_col * 2, vt.data_ptr()
     a.o_lo_off = 0 if out_split != 2 else ((o_lo_col - o_col) if o_lo_col is not None else inner)
     a.o_mx = int(out_split == 3)
     if (q_lo_col is None) != (k_lo_col is None):
@@ -1559,6 +1541,21 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, he
     return out
 
 
+def _fill_attn(a: AttnArgs, q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, o_col: int, heads: int, head_dim: int,
+               Lk: int, scale: float) -> bool:
+    """What the 16-bit and the MXFP8 form share (q, k, vt: the element tensors - the codes of an Mxfp8): extents, leading dimensions, batch
+    strides (one K / V for the whole batch when k has one image and q more: stride 0) and the 16-bit output. Returns that broadcast flag."""
+    B, Lq = q.shape[0], q.shape[1]
+    bcast = k.shape[0] == 1 and B > 1
+    a.B, a.H, a.D, a.Lq, a.Lk = B, heads, head_dim, Lq, Lk
+    a.q_ld, a.k_ld, a.vt_ld, a.o_ld = q.shape[-1], k.shape[-1], vt.shape[-1], out.shape[-1]
+    a.q_bstride, a.o_bstride = Lq * q.shape[-1], Lq * out.shape[-1]
+    a.k_bstride, a.vt_bstride = (0, 0) if bcast else (k.shape[1] * k.shape[-1], vt.shape[1] * vt.shape[-1])
+    a.o = out.data_ptr() + o_col * 2
+    a.scale = scale
+    return bcast
+
+
 def _attention_mxfp8(q: Mxfp8, k: Mxfp8, vt: Mxfp8, heads: int, head_dim: int, scale: float, q_col: int, k_col: int, Lk: Optional[int],
                      out: Optional[torch.Tensor], o_col: int) -> torch.Tensor:
     """attention() on OMGSR_EL_MXFP8 q / k / V^T (mxfp8_attn_kernel, ABI v19)."""
@@ -1573,7 +1570,6 @@ def _attention_mxfp8(q: Mxfp8, k: Mxfp8, vt: Mxfp8, heads: int, head_dim: int, s
     if q_col % 128 or k_col % 128:
         raise ValueError("attention: MXFP8 q / k columns must be multiples of 128")
     B, Lq = q.codes.shape[0], q.codes.shape[1]
-    Bk = k.codes.shape[0]
     Lk = Lk if Lk is not None else k.codes.shape[1]
     inner = heads * head_dim
     ld = vt.codes.shape[-1]
@@ -1584,20 +1580,14 @@ def _attention_mxfp8(q: Mxfp8, k: Mxfp8, vt: Mxfp8, heads: int, head_dim: int, s
     if out is None:
         out = torch.empty((B, Lq, inner), device=q.codes.device, dtype=torch.bfloat16)
     _req(out, torch.bfloat16, "out")
-    bcast = Bk == 1 and B > 1
     a = AttnArgs()
+    bcast = _fill_attn(a, q.codes, k.codes, vt.codes, out, o_col, heads, head_dim, Lk, scale)
     a.qkv_el = EL_MXFP8
     a.q, a.k, a.vt = q.codes.data_ptr() + q_col, k.codes.data_ptr() + k_col, vt.codes.data_ptr()
     a.q_scale, a.k_scale, a.vt_scale = q.scales.data_ptr() + q_col // 32, k.scales.data_ptr() + k_col // 32, vt.scales.data_ptr()
-    a.o = out.data_ptr() + o_col * 2
-    a.B, a.H, a.D, a.Lq, a.Lk = B, heads, head_dim, Lq, Lk
-    a.q_ld, a.k_ld, a.vt_ld, a.o_ld = q.codes.shape[-1], k.codes.shape[-1], ld, out.shape[-1]
     a.q_sld, a.k_sld, a.vt_sld = q.scales.shape[-1], k.scales.shape[-1], vt.scales.shape[-1]
-    a.q_bstride, a.q_sbstride = Lq * a.q_ld, Lq * a.q_sld
-    a.k_bstride, a.k_sbstride = (0, 0) if bcast else (k.codes.shape[1] * a.k_ld, k.codes.shape[1] * a.k_sld)
-    a.vt_bstride, a.vt_sbstride = (0, 0) if bcast else (inner * ld, inner * a.vt_sld)
-    a.o_bstride = Lq * out.shape[-1]
-    a.scale = scale
+    a.q_sbstride = Lq * a.q_sld
+    a.k_sbstride, a.vt_sbstride = (0, 0) if bcast else (k.codes.shape[1] * a.k_sld, inner * a.vt_sld)
     check(_lib.load().omgsr_attention(C.byref(a), _stream()), "omgsr_attention")
     return out
 
@@ -1648,7 +1638,7 @@ def rmsnorm_rope_mxfp8(x: torch.Tensor, w: torch.Tensor, cos: Optional[torch.Ten
     if cos is not None and (cos.shape[0] < pos0 + L or sin.shape[0] < pos0 + L or cos.shape[-1] != head_dim):
         raise ValueError(f"rmsnorm_rope_mxfp8: rope tables {tuple(cos.shape)} do not cover positions {pos0}..{pos0 + L - 1} x {head_dim}")
     if out is None:
-        out = Mxfp8(torch.empty((B, L, ld), device=x.device, dtype=torch.uint8), torch.empty((B, L, ld // 32), device=x.device, dtype=torch.uint8))
+        out = _mxfp8_like(x)
     elif out.codes.shape != (B, L, ld) or out.scales.shape != (B, L, ld // 32) or not (out.codes.is_contiguous() and out.scales.is_contiguous()):
         raise ValueError("rmsnorm_rope_mxfp8: `out` does not match x")
     check(_lib.load().omgsr_rmsnorm_rope_mxfp8(x.data_ptr(), w.data_ptr(), _ptr(w_after), split_at, _ptr(cos), _ptr(sin), B, L, heads, head_dim,
