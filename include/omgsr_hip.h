@@ -188,6 +188,14 @@ typedef struct omgsr_igemm_args {
     const uint8_t* in_scale;    /* E8M0 [batch][M][Cin / 32] */
     const uint8_t* w_scale;     /* E8M0 [Cout_pad][K_pad / 32] (w_bstride / 32 per grid.z entry) */
 } omgsr_igemm_args;
+/* Additive under ABI v22 (a new entry point; no struct changes): omgsr_igemm for an `mxf8` = 1 problem whose output is written in the
+ * OMGSR_EL_MXFP8 form, the operand of the next MXFP8 GEMM - the codes and scale bytes omgsr_quantize_mxfp8 makes of the bf16 output the
+ * problem would otherwise store. a->out is the code plane (uint8, rows of out_ld bytes, 0 = Cout; out_bstride in bytes, the scale plane's
+ * batch stride is out_bstride / 32), out_scale the E8M0 plane [batch][M][out_scale_ld] (0 = Cout / 32). A column offset into wider planes is
+ * folded into both pointers (offset % 128 == 0). With bias and act; out_dtype OMGSR_OUT_BF16, NHWC, out_mx 0, Cout % 32 == 0, out_ld % 16 == 0,
+ * a->out 16-byte aligned. Residual, gate, GroupNorm statistics, out_lo_off, LAYOUT_T and a problem that is not mxf8 return OMGSR_E_SHAPE
+ * (never another kernel). Rows >= M and columns >= Cout are not written. Timing: kind OMGSR_TK_IGEMM, variant 18. */
+int omgsr_igemm_out_mxfp8(const omgsr_igemm_args* a, void* out_scale, int64_t out_scale_ld, void* stream);
 /* 1 when omgsr_igemm / omgsr_igemm_multi would run these arguments with the GroupNorm apply fused into the conv's patch producer (the
  * fields above may still be unset: the answer depends on geometry, operand / weight form, compute type and `in_el` only; for a problem of a
  * launch group call omgsr_igemm_multi_plan first). 0: run omgsr_groupnorm_apply and hand the conv its operand as before. */
@@ -349,6 +357,17 @@ int omgsr_layernorm(const void* x, void* y, const float* a, const float* b, int6
  * its first K columns: codes [rows][K], scales [rows][K / 32]. K % 128 == 0, x_ld >= K, x_ld % 8 == 0. Activations of the fp8 tier (one
  * pass per LayerNorm output / attention output / FF hidden, shared by every consumer) and weights at pack time. */
 int omgsr_quantize_mxfp8(const void* x, int32_t x_el, int64_t rows, int32_t K, int64_t x_ld, void* codes, void* scales, void* stream);
+/* Additive under ABI v22: omgsr_quantize_mxfp8 with pitches for the output planes - codes [rows][c_ld] bytes, scales [rows][s_ld] bytes (c_ld >= K,
+ * c_ld % 16 == 0, `codes` 16-byte aligned, s_ld >= K / 32): quantises a tensor into columns of a wider OMGSR_EL_MXFP8 operand (the attention
+ * output into the single block's [attn | mlp] operand). The bytes written are omgsr_quantize_mxfp8's; nothing outside the window is touched. */
+int omgsr_quantize_mxfp8_ld(const void* x, int32_t x_el, int64_t rows, int32_t K, int64_t x_ld, void* codes, void* scales, int64_t c_ld,
+                            int64_t s_ld, void* stream);
+/* Additive under ABI v22: omgsr_layernorm (x_el OMGSR_EL_16, bf16 compute type) whose result is written in the OMGSR_EL_MXFP8 form - codes uint8
+ * [rows][c_ld], scales uint8 [rows][s_ld] - with the bytes of "omgsr_layernorm writes bf16, omgsr_quantize_mxfp8 reads it": the fp32 result
+ * is rounded to bf16 by the 16-bit store's conversion in registers and quantised from there. C % 128 == 0, C <= 4096, c_ld >= C,
+ * c_ld % 8 == 0, `codes` 8-byte aligned, s_ld >= C / 32; anything else (fp32 input, fp16 compute type) returns OMGSR_E_SHAPE. Timing kind OMGSR_TK_LN. */
+int omgsr_layernorm_mxfp8(const void* x, const float* a, const float* b, int64_t rows, int32_t C, float eps, int32_t x_el, void* codes,
+                          void* scales, int64_t c_ld, int64_t s_ld, void* stream);
 /* Stream tensor -> MFMA operand: y = x rounded to the compute type (y_el OMGSR_EL_16) or its two-term split
  * (OMGSR_EL_SPLIT); x f32 [rows][C], C % 8 == 0. (Inputs of convs that no norm precedes: up / down-sampling convs,
  * 1x1 shortcuts, conv_in, proj_out, post_quant_conv.) */

@@ -35,6 +35,7 @@ bool igemm_gmx_ok(const omgsr_igemm_args& a);
 int igemm_gmx_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
 bool mxfp8_gemm_ok(const omgsr_igemm_args& a);                                 // gemm_mxfp8.hip: OMGSR_EL_MXFP8 operand and weight
 int mxfp8_gemm_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
+int mxfp8_gemm_out8_launch(const omgsr_igemm_args& a, IgemmGeo g, unsigned char* out_scale, int64_t out_scale_ld, hipStream_t st);   // gemm_mxfp8_out8.hip
 int igemm_halo_tiles(const omgsr_igemm_args& a, bool phase = false);
 bool igemm_halo_out6_ok(const omgsr_igemm_args& a);   // igemm_halo_out6.hip: the instantiations whose epilogue writes OMGSR_EL_MX6 can run this problem
 int igemm_halo_flat(const omgsr_igemm_args& a);      // pitch of the FLAT form the halo kernel would use for this problem (narrow maps), 0 = spatial tiles
@@ -566,13 +567,13 @@ int validate_args(omgsr_igemm_args& a) {
     return 0;
 }
 
-void work_of(const omgsr_igemm_args& a, double* flops, double* bytes) {
+void work_of(const omgsr_igemm_args& a, double* flops, double* bytes, const bool out8 = false) {
     const int64_t M64 = (int64_t)a.N * a.Ho * a.Wo;
     const int logical_cols = (a.act == OMGSR_ACT_GEGLU) ? 2 * a.Cout : a.Cout;
     const int ksegs = 1 + (a.in_split ? 1 : 0) + (a.w_split ? 1 : 0);
     // algorithmic work: a split operand's / weight's extra K segments are precision overhead, not useful FLOPs
     *flops = 2.0 * (double)M64 * (double)a.R * a.S * (a.Cin / ksegs) * (double)logical_cols * a.batch;
-    const double out_b = (a.out_dtype == OMGSR_OUT_F32 ? 4.0 : (a.out_lo_off ? 4.0 : 2.0)), res_b = a.residual ? (a.res_el == OMGSR_EL_F32 ? 4.0 : 2.0) : 0.0;
+    const double out_b = out8 ? 1.0 + 1.0 / 32.0 : (a.out_dtype == OMGSR_OUT_F32 ? 4.0 : (a.out_lo_off ? 4.0 : 2.0)), res_b = a.residual ? (a.res_el == OMGSR_EL_F32 ? 4.0 : 2.0) : 0.0;
     const double eb = a.mxf8 ? 1.0 + 1.0 / 32.0 : 2.0;        // fp8 codes + their E8M0 scales
     *bytes = (eb * ((double)a.N * a.H * a.W * (a.in_ld > 0 ? a.in_ld : a.Cin) + (double)a.Cout_pad * a.K_pad) + (double)M64 * a.Cout * (out_b + res_b)) * a.batch;
 }
@@ -765,6 +766,35 @@ extern "C" int omgsr_conv_mxfp8_multi(const omgsr_igemm_args* args, int32_t coun
         if (rc != 0) return rc;
     }
     return 0;
+}
+
+// Additive under ABI v22: an mxf8 problem whose output is written in the OMGSR_EL_MXFP8 form (include/omgsr_hip.h) - mxfp8_gemm_kernel's OUT8
+// instantiation or nothing. The scale plane travels next to the argument block, whose layout does not change.
+extern "C" int omgsr_igemm_out_mxfp8(const omgsr_igemm_args* ap, void* out_scale, int64_t out_scale_ld, void* stream) {
+    if (!ap || !out_scale) return OMGSR_E_BADARG;
+    omgsr_igemm_args a = *ap;
+    // what this form does not go with is OMGSR_E_SHAPE whatever else the block says (checked before the general rules)
+    if (a.out_mx != 0 || !a.mxf8 || a.out_dtype != OMGSR_OUT_BF16 || a.out_layout != OMGSR_LAYOUT_NHWC || a.Cout <= 0 || (a.Cout & 31) || a.out_ld < 0 ||
+        (a.out_ld & 15) || (a.out_ld > 0 && a.out_ld < a.Cout) || out_scale_ld < 0 || (out_scale_ld > 0 && out_scale_ld < a.Cout / 32) || a.residual || a.gate ||
+        a.gn_partial || a.out_lo_off || (a.out_bstride & 31) || ((uintptr_t)a.out & 15) || a.act == OMGSR_ACT_GEGLU)
+        return OMGSR_E_SHAPE;
+    {
+        const int rc = validate_args(a);           // (mxf8: mxfp8_gemm_ok)
+        if (rc != 0) return rc;
+    }
+    const int64_t M64 = (int64_t)a.N * a.Ho * a.Wo;
+    Geo g{};
+    g.M = (int)M64;
+    g.HoWo = a.Ho * a.Wo;
+    g.Hv = a.H;
+    g.Wv = a.W;
+    g.nk = a.K_pad / BK;
+    hipStream_t st = (hipStream_t)stream;
+    double flops, bytes;
+    work_of(a, &flops, &bytes, true);
+    omgsr::TimingScope ts(OMGSR_TK_IGEMM, flops, bytes, st, M64 * a.batch, a.Cout, (long long)a.Cin);
+    ts.rec.variant = 18;                           // the same kernel body as the 16-bit form
+    return omgsr::mxfp8_gemm_out8_launch(a, g, (unsigned char*)out_scale, out_scale_ld > 0 ? out_scale_ld : a.Cout / 32, st);
 }
 
 extern "C" int omgsr_igemm(const omgsr_igemm_args* ap, void* stream) {

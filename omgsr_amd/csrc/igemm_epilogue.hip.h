@@ -12,6 +12,7 @@
 #pragma once
 #include "common.hip.h"
 #include "../../include/omgsr_hip.h"
+#include "mxfp8.hip.h"
 #include <type_traits>
 
 OMGSR_DEVINL void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -20,10 +21,13 @@ OMGSR_DEVINL void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "me
 // (pixels) mb[i] .. mb[i] + nvalid[i] - 1; n_base: first PACKED column of the wave tile (GEGLU: packed
 // [32 a | 32 g] per 64). Must be called by every wave of the block.
 // RES32: the residual is an fp32 stream tensor (accurate tier) instead of the 16-bit compute type.
-template <typename T, int WTN, int FM, int FN, bool RES32, bool OUT6 = false>
+// OUT8 only (omgsr_igemm_out_mxfp8): the scale plane of the OMGSR_EL_MXFP8 output and its row pitch - not part of omgsr_igemm_args
+struct IgemmOut8 { unsigned char* scale; int64_t ld; };
+
+template <typename T, int WTN, int FM, int FN, bool RES32, bool OUT6 = false, bool OUT8 = false>
 OMGSR_DEVINL void igemm_epilogue_impl(const omgsr_igemm_args& p, f32x16_t (&acc)[FM][FN], float* epi, const int lane,
                                       const int (&mb)[FM], const int (&nvalid)[FM], const int n_base, const int bz,
-                                      float* gn_dst, const int gn_howo, const int pxs, const int flat_base) {
+                                      float* gn_dst, const int gn_howo, const int pxs, const int flat_base, const IgemmOut8& o8) {
     // pxs: distance in output pixels between consecutive rows of a fragment row block (1; 2 when the block is one phase of a
     // phase-decomposed upsampling conv: its pixels land on every other column). A residual is not supported with pxs == 2.
     // pxs < 0 (halo kernel, FLAT form, fast path only): the rows of a block are consecutive positions f = mb[i] + row of the image's
@@ -234,6 +238,20 @@ OMGSR_DEVINL void igemm_epilogue_impl(const omgsr_igemm_args& p, f32x16_t (&acc)
                     }
                     bool sok;
                     const int spix = opix(i, row, sok);
+                    if constexpr (OUT8) {      // OUT8 (omgsr_igemm_out_mxfp8; mxfp8_gemm_kernel's own instantiation, gemm_mxfp8_out8.hip): the output is the
+                                               // OMGSR_EL_MXFP8 operand of the next MXFP8 GEMM - the value the 16-bit store would round to bf16, quantised by
+                                               // omgsr_quantize_mxfp8's rule. WTN = 64: 8 lanes per row, a lane quad = one 32-column block of one row
+                                               // (Cout % 32 == 0: all-live or all-dead); every lane calls, only the stores are predicated. No gate, residual
+                                               // or statistics (omgsr_igemm_out_mxfp8 refuses them)
+                        static_assert(!OUT8 || (WTN == 64 && std::is_same<T, bf16_t>::value && !RES32), "OUT8: mxfp8_gemm_kernel's wave tile");
+                        int s8;
+                        const u32x2_t c8 = mxfp8_quad_octet(v, s8);
+                        if (sok && col_ok) {
+                            unsigned char* ob = reinterpret_cast<unsigned char*>(p.out) + (int64_t)bz * p.out_bstride;
+                            *reinterpret_cast<u32x2_t*>(ob + (int64_t)spix * ldo + n_out) = c8;
+                            if ((lane & 3) == 0) o8.scale[(int64_t)bz * (p.out_bstride >> 5) + (int64_t)spix * o8.ld + (n_out >> 5)] = (unsigned char)s8;
+                        }
+                    } else
                     if constexpr (OUT6) {      // OUT6 (a template flag with its own kernel instantiations, igemm_halo_out6.hip: as a run-time branch next to the
                                                // other output forms the cooperative store spilled every kernel that includes this epilogue): the output is the
                                                // OMGSR_EL_MX6 operand of an up-sampling conv. Lane quads hold the four octets of a block (consecutive lanes =
@@ -414,18 +432,21 @@ OMGSR_DEVINL void igemm_epilogue_impl(const omgsr_igemm_args& p, f32x16_t (&acc)
     flush_ovf();
 }
 
-template <typename T, int WTN, int FM, int FN, bool OUT6 = false>
+template <typename T, int WTN, int FM, int FN, bool OUT6 = false, bool OUT8 = false>
 OMGSR_DEVINL void igemm_epilogue(const omgsr_igemm_args& p, f32x16_t (&acc)[FM][FN], float* epi, const int lane,
                                  const int (&mb)[FM], const int (&nvalid)[FM], const int n_base, const int bz,
-                                 float* gn_dst = nullptr, const int gn_howo = 0, const int pxs = 1, const int flat_base = 0) {
-    if (p.res_el == OMGSR_EL_F32 && p.residual) igemm_epilogue_impl<T, WTN, FM, FN, true, OUT6>(p, acc, epi, lane, mb, nvalid, n_base, bz, gn_dst, gn_howo, pxs, flat_base);
-    else igemm_epilogue_impl<T, WTN, FM, FN, false, OUT6>(p, acc, epi, lane, mb, nvalid, n_base, bz, gn_dst, gn_howo, pxs, flat_base);
+                                 float* gn_dst = nullptr, const int gn_howo = 0, const int pxs = 1, const int flat_base = 0,
+                                 const IgemmOut8 o8 = IgemmOut8{nullptr, 0}) {
+    if constexpr (OUT8) igemm_epilogue_impl<T, WTN, FM, FN, false, false, true>(p, acc, epi, lane, mb, nvalid, n_base, bz, gn_dst, gn_howo, pxs, flat_base, o8);
+    else if (p.res_el == OMGSR_EL_F32 && p.residual) igemm_epilogue_impl<T, WTN, FM, FN, true, OUT6>(p, acc, epi, lane, mb, nvalid, n_base, bz, gn_dst, gn_howo, pxs, flat_base, o8);
+    else igemm_epilogue_impl<T, WTN, FM, FN, false, OUT6>(p, acc, epi, lane, mb, nvalid, n_base, bz, gn_dst, gn_howo, pxs, flat_base, o8);
 }
 
 // linear-M helper for the GEMM-shaped kernels: row block i starts at m_base + 32*i
-template <typename T, int WTN, int FM, int FN>
+template <typename T, int WTN, int FM, int FN, bool OUT8 = false>
 OMGSR_DEVINL void igemm_epilogue_linear(const omgsr_igemm_args& p, const int M, f32x16_t (&acc)[FM][FN], float* epi,
-                                        const int lane, const int m_base, const int n_base, const int bz, const int gn_howo = 0) {
+                                        const int lane, const int m_base, const int n_base, const int bz, const int gn_howo = 0,
+                                        const IgemmOut8 o8 = IgemmOut8{nullptr, 0}) {
     int mb[FM], nv[FM];
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
@@ -433,7 +454,7 @@ OMGSR_DEVINL void igemm_epilogue_linear(const omgsr_igemm_args& p, const int M, 
         const int left = M - mb[i];
         nv[i] = left < 0 ? 0 : (left > 32 ? 32 : left);
     }
-    igemm_epilogue<T, WTN, FM, FN>(p, acc, epi, lane, mb, nv, n_base, bz, nullptr, gn_howo);
+    igemm_epilogue<T, WTN, FM, FN, false, OUT8>(p, acc, epi, lane, mb, nv, n_base, bz, nullptr, gn_howo, 1, 0, o8);
 }
 
 struct IgemmGeo {

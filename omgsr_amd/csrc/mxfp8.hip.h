@@ -1,5 +1,5 @@
 // The OMGSR_EL_MXFP8 element rule (include/omgsr_hip.h), shared by the quantiser (gemm_mxfp8.hip) and the kernels that write the form
-// directly (norm.hip: rmsnorm_rope_mxfp8_kernel).
+// directly (norm.hip: rmsnorm_rope_mxfp8_kernel, gn_apply_mxfp8_kernel, the LayerNorm's LnMx8 forms; igemm_epilogue.hip.h: OUT8).
 #pragma once
 #include "common.hip.h"
 
@@ -29,4 +29,20 @@ OMGSR_DEVINL int mxfp8_scale(const float mx) {
 OMGSR_DEVINL unsigned mxfp8_code(const float v, const int s) {
     const float mul = __uint_as_float((unsigned)(254 - s) << 23);      // 2^(127 - s): a normal float for every s in [0, 246]
     return e4m3_rne(fminf(fmaxf(v * mul, -448.0f), 448.0f));
+}
+
+// A fused producer's octet: the lane's 8 fp32 results rounded to bf16 by the 16-bit store's own conversion (pack8<bf16_t>), then the quantiser's
+// rule on those rounded values - the bytes of "store bf16, run omgsr_quantize_mxfp8". The four octets of the 32-value block sit in one lane quad
+// (consecutive lanes = consecutive octets, the quad all-live): its maximum is two exchanges. Returns the codes; s = the block's E8M0 byte.
+OMGSR_DEVINL u32x2_t mxfp8_quad_octet(const float (&v)[8], int& s) {
+    float f[8];
+    unpack8<bf16_t>(pack8<bf16_t>(v), f);
+    float mx = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(f[e]));
+    s = mxfp8_scale(quad_max(mx));
+    u32x2_t out = {0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[e >> 2] |= mxfp8_code(f[e], s) << (8 * (e & 3));
+    return out;
 }

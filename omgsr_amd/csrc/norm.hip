@@ -408,10 +408,26 @@ OMGSR_DEVINL void load_affine8(const float* __restrict__ v, const int c, const f
 // All RPW*MAXCH 16-byte loads of a wave are issued before the first reduction (one row per wave kept a single load
 // in flight: 1.05 TB/s on the UNet's [147456, 320] token matrices), the RPW butterfly chains interleave, and the
 // affine vectors are fetched once per wave.
+// YEL = OMGSR_EL_MXFP8 (omgsr_layernorm_mxfp8, additive under ABI v22): y is the code plane and `mx` carries the scale plane and the two pitches; the result
+// is rounded to bf16 as the 16-bit store rounds it and quantised in registers (mxfp8_quad_octet: C % 128 == 0 keeps every lane quad of
+// octets lane + 64 i all-live or all-dead). Every other form takes the empty LnPlain and compiles as before.
+struct LnMx8 { unsigned char* scales; int64_t c_ld, s_ld; };
+struct LnPlain {};
+template <int YEL> using ln_extra_t = typename std::conditional<YEL == OMGSR_EL_MXFP8, LnMx8, LnPlain>::type;
+template <int YEL>
+OMGSR_DEVINL void ln_store8_mxfp8(void* y, const ln_extra_t<YEL>& mx, const int64_t row, const int c8, const float (&o8)[8]) {
+    if constexpr (YEL == OMGSR_EL_MXFP8) {
+        int s;
+        const u32x2_t out = mxfp8_quad_octet(o8, s);
+        *reinterpret_cast<u32x2_t*>(reinterpret_cast<unsigned char*>(y) + row * mx.c_ld + c8 * 8) = out;
+        if ((c8 & 3) == 0) mx.scales[row * mx.s_ld + (c8 >> 2)] = (unsigned char)s;
+    }
+}
+
 template <typename T, int MAXCH, int RPW, bool XF32 = false, int YEL = 0>
 __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__ x, void* __restrict__ y,
                                                          const float* __restrict__ a, const float* __restrict__ b,
-                                                         int64_t rows, int C, float eps) {
+                                                         int64_t rows, int C, float eps, const ln_extra_t<YEL> mx) {
     const int lane = threadIdx.x & 63;
     const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
     if (row0 >= rows) return;
@@ -480,7 +496,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
                     o8[e] = (f[r][i][e] - mu[r]) * rs * (PRE ? av[PRE ? i : 0][e] : ga[e]) + (PRE ? bv[PRE ? i : 0][e] : be[e]);
-                if constexpr (YEL == 3) {
+                if constexpr (YEL == OMGSR_EL_MXFP8) ln_store8_mxfp8<YEL>(y, mx, row0 + r, c8, o8);
+                else if constexpr (YEL == 3) {
                     if constexpr (std::is_same<T, f16_t>::value) store8_mx<T>(y, (row0 + r) * 4 * (int64_t)C, C, c8 * 8, o8);   // OMGSR_EL_MX row: 4C bytes
                 } else store8<T, YEL>(y, (row0 + r) * (YEL == 2 ? 2 * C : C) + c8 * 8, C, o8);
             }
@@ -493,7 +510,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
 template <typename T, int MAXV, bool XF32 = false, int YEL = 0>
 __global__ __launch_bounds__(256) void layernorm_block_kernel(const void* __restrict__ x, void* __restrict__ y,
                                                                const float* __restrict__ a, const float* __restrict__ b,
-                                                               int C, float eps) {
+                                                               int C, float eps, const ln_extra_t<YEL> mx) {
     __shared__ float red[2][4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int64_t row = blockIdx.x;
@@ -533,7 +550,8 @@ __global__ __launch_bounds__(256) void layernorm_block_kernel(const void* __rest
             load_affine8(a, c8 * 8, 1.0f, ga); load_affine8(b, c8 * 8, 0.0f, be);
 #pragma unroll
             for (int e = 0; e < 8; ++e) o8[e] = (f[i][e] - mu) * rs * ga[e] + be[e];
-            if constexpr (YEL == 3) {
+            if constexpr (YEL == OMGSR_EL_MXFP8) ln_store8_mxfp8<YEL>(y, mx, row, c8, o8);       // (octets t + 256 i: quads as in layernorm_kernel)
+            else if constexpr (YEL == 3) {
                 if constexpr (std::is_same<T, f16_t>::value) store8_mx<T>(y, row * 4 * (int64_t)C, C, c8 * 8, o8);
             } else store8<T, YEL>(y, row * (YEL == 2 ? 2 * C : C) + c8 * 8, C, o8);
         }
@@ -1164,14 +1182,18 @@ extern "C" int omgsr_groupnorm_apply_multi(const omgsr_gn_apply_group* groups, i
 
 namespace {
 template <bool XF32, int YEL>
-int layernorm_launch(const void* x, void* y, const float* a, const float* b, int64_t rows, int32_t C, float eps, hipStream_t st) {
+int layernorm_launch(const void* x, void* y, const float* a, const float* b, int64_t rows, int32_t C, float eps, hipStream_t st,
+                     const ln_extra_t<YEL> mx = ln_extra_t<YEL>{}) {
     const int nch = ((C >> 3) + 63) / 64;
+    // (the MXFP8 form exists for the bf16 compute type only: no fp16 instantiation)
+#define LN_GO(...) do { if constexpr (YEL == OMGSR_EL_MXFP8) { using T = bf16_t; __VA_ARGS__; } else OMGSR_DISPATCH_T(__VA_ARGS__); } while (0)
     auto grid = [&](int rpw) { return dim3((unsigned)((rows + 4 * rpw - 1) / (4 * rpw))); };
-    if (nch <= 1) OMGSR_DISPATCH_T(hipLaunchKernelGGL((layernorm_kernel<T, 1, 4, XF32, YEL>), grid(4), dim3(256), 0, st, x, y, a, b, rows, C, eps));
-    else if (nch <= 2) OMGSR_DISPATCH_T(hipLaunchKernelGGL((layernorm_kernel<T, 2, 4, XF32, YEL>), grid(4), dim3(256), 0, st, x, y, a, b, rows, C, eps));
-    else if (nch <= 3) OMGSR_DISPATCH_T(hipLaunchKernelGGL((layernorm_kernel<T, 3, 2, XF32, YEL>), grid(2), dim3(256), 0, st, x, y, a, b, rows, C, eps));
+    if (nch <= 1) LN_GO(hipLaunchKernelGGL((layernorm_kernel<T, 1, 4, XF32, YEL>), grid(4), dim3(256), 0, st, x, y, a, b, rows, C, eps, mx));
+    else if (nch <= 2) LN_GO(hipLaunchKernelGGL((layernorm_kernel<T, 2, 4, XF32, YEL>), grid(4), dim3(256), 0, st, x, y, a, b, rows, C, eps, mx));
+    else if (nch <= 3) LN_GO(hipLaunchKernelGGL((layernorm_kernel<T, 3, 2, XF32, YEL>), grid(2), dim3(256), 0, st, x, y, a, b, rows, C, eps, mx));
     else if (rows >= (1ll << 31)) return OMGSR_E_SHAPE;
-    else OMGSR_DISPATCH_T(hipLaunchKernelGGL((layernorm_block_kernel<T, 2, XF32, YEL>), dim3((unsigned)rows), dim3(256), 0, st, x, y, a, b, C, eps));
+    else LN_GO(hipLaunchKernelGGL((layernorm_block_kernel<T, 2, XF32, YEL>), dim3((unsigned)rows), dim3(256), 0, st, x, y, a, b, C, eps, mx));
+#undef LN_GO
     return (int)hipGetLastError();
 }
 }  // namespace
@@ -1190,6 +1212,16 @@ extern "C" int omgsr_layernorm(const void* x, void* y, const float* a, const flo
     if (x_el == OMGSR_EL_F32) return layernorm_launch<true, 0>(x, y, a, b, rows, C, eps, st);
     if (y_el == OMGSR_EL_SPLIT) return layernorm_launch<false, 2>(x, y, a, b, rows, C, eps, st);
     return layernorm_launch<false, 0>(x, y, a, b, rows, C, eps, st);
+}
+
+extern "C" int omgsr_layernorm_mxfp8(const void* x, const float* a, const float* b, int64_t rows, int32_t C, float eps, int32_t x_el, void* codes,
+                                     void* scales, int64_t c_ld, int64_t s_ld, void* stream) {
+    if (!x || !codes || !scales || rows <= 0 || C <= 0) return OMGSR_E_BADARG;
+    if (x_el != OMGSR_EL_16 || omgsr::compute_dtype() != 0 || (C % 128) || C > 4096 || c_ld < C || (c_ld & 7) || s_ld < C / 32 ||
+        ((uintptr_t)codes & 7)) return OMGSR_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    omgsr::TimingScope ts(OMGSR_TK_LN, 0.0, (2.0 + 1.0 + 1.0 / 32.0) * (double)rows * C, st);
+    return layernorm_launch<false, OMGSR_EL_MXFP8>(x, codes, a, b, rows, C, eps, st, LnMx8{(unsigned char*)scales, c_ld, s_ld});
 }
 
 extern "C" int omgsr_softmax_rows(const float* s, void* p, int64_t rows, int32_t L, int32_t Lvalid, void* stream) {

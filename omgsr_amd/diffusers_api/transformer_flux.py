@@ -86,6 +86,25 @@ def _fp8_in(x: torch.Tensor, *layers):
     return [xq if l.fp8 else x for l in layers]
 
 
+def fused_quant_plan(flags: dict, switch: Optional[dict] = None, dim: Optional[int] = None, hidden: Optional[int] = None) -> dict:
+    """Which producers of a block write their MXFP8 output themselves (the fp8 tier), from the `.fp8` flags of the layers that read
+    them: a producer fuses only when EVERY consumer of its output is an fp8 layer - a mixed set (a narrowed precision policy) keeps today's
+    path, bf16 output + _fp8_in. `switch`: ops.FP8_FUSED_QUANT ({"layernorm", "gemm"}: OMGSR_FP8_FUSED_QUANT).
+    Double block - flags to_q (to_k moves with it), to_v, add_q, add_v, ff0, ff2, ffc0, ffc2 -> ln1, ln1_ctx, ln2, ln2_ctx (LayerNorm writes
+    Mxfp8), ff, ffc (net[0].proj writes the MXFP8 hidden). Single block - flags to_q, to_v, proj_mlp, proj_out -> ln, cat8 (proj_mlp writes
+    columns [D, Kc) of the Mxfp8 [attn | mlp] operand, the attention output is quantised into [0, D)).
+    dim / hidden (the block's width and its FF / MLP hidden width, when given): a shape the fused kernels do not take - a LayerNorm row that
+    is no multiple of 128 or wider than 4096, an MXFP8 output that is not whole 128-column groups - keeps the pass form too."""
+    sw = ops.FP8_FUSED_QUANT if switch is None else switch
+    f = lambda *names: all(bool(flags[n]) for n in names)
+    ln = bool(sw["layernorm"]) and (dim is None or (dim % 128 == 0 and dim <= 4096))
+    gemm = bool(sw["gemm"]) and (hidden is None or hidden % 128 == 0) and (dim is None or "proj_mlp" not in flags or dim % 128 == 0)
+    if "proj_mlp" in flags:
+        return dict(ln=ln and f("to_q", "to_v", "proj_mlp"), cat8=gemm and f("proj_mlp", "proj_out"))
+    return dict(ln1=ln and f("to_q", "to_v"), ln1_ctx=ln and f("add_q", "add_v"), ln2=ln and f("ff0"), ln2_ctx=ln and f("ffc0"),
+                ff=gemm and f("ff0", "ff2"), ffc=gemm and f("ffc0", "ffc2"))
+
+
 class GELUProj(nn.Module):
     def __init__(self, dim_in: int, dim_out: int):
         super().__init__()
@@ -97,8 +116,12 @@ class FluxFeedForward(nn.Module):
         super().__init__()
         self.net = nn.ModuleList([GELUProj(dim, dim * mult), nn.Dropout(0.0), Linear(dim * mult, dim)])
 
-    def run(self, xn, residual, gate):
-        h = self.net[0].proj.nhwc(xn, act=ops.ACT_GELU_TANH, out_dtype=ops.OUT_BF16, out_split=self.net[2].in_split())
+    def run(self, xn, residual, gate, hidden8: bool = False):
+        """hidden8 (fused_quant_plan: net[0].proj and net[2] are both fp8): the GELU hidden leaves net[0].proj's epilogue as an Mxfp8."""
+        if hidden8:
+            h = self.net[0].proj.nhwc(xn, act=ops.ACT_GELU_TANH, out_mxfp8=True)
+        else:
+            h = self.net[0].proj.nhwc(xn, act=ops.ACT_GELU_TANH, out_dtype=ops.OUT_BF16, out_split=self.net[2].in_split())
         return self.net[2].nhwc(h, residual=residual, gate=gate)
 
 
@@ -140,12 +163,17 @@ class FluxTransformerBlock(nn.Module):
         at = self.attn
         Lc, Li = c.shape[1], h.shape[1]
         mi, mc = mod["img"], mod["ctx"]
-        hn = ops.layer_norm(h, mi["a1"], mi["b1"], 1e-6, split=at.to_q.in_split())
-        cn = ops.layer_norm(c, mc["a1"], mc["b1"], 1e-6, split=at.add_q_proj.in_split())
+        plan = fused_quant_plan(dict(to_q=at.to_q.fp8, to_v=at.to_v.fp8, add_q=at.add_q_proj.fp8, add_v=at.add_v_proj.fp8,
+                                     ff0=self.ff.net[0].proj.fp8, ff2=self.ff.net[2].fp8, ffc0=self.ff_context.net[0].proj.fp8,
+                                     ffc2=self.ff_context.net[2].fp8), dim=h.shape[-1], hidden=self.ff.net[2].in_features)
+        hn = ops.layer_norm_mxfp8(h, mi["a1"], mi["b1"], 1e-6) if plan["ln1"] else ops.layer_norm(h, mi["a1"], mi["b1"], 1e-6, split=at.to_q.in_split())
+        cn = ops.layer_norm_mxfp8(c, mc["a1"], mc["b1"], 1e-6) if plan["ln1_ctx"] else \
+            ops.layer_norm(c, mc["a1"], mc["b1"], 1e-6, split=at.add_q_proj.in_split())
         osp = at.to_out[0].in_split()                      # to_out and to_add_out read one buffer: same form (precision.check_policy)
         qk, vt, o = ws["qk"], ws["vt"], ws["o2" if osp == 2 else "o"]
-        cn_qk, cn_v = _fp8_in(cn, at.add_q_proj, at.add_v_proj)      # (fp8 tier: each LayerNorm output is quantised once)
-        hn_qk, hn_v = _fp8_in(hn, at.to_q, at.to_v)
+        # (fp8 tier: each LayerNorm output is quantised once - by the LayerNorm itself where the plan says so)
+        cn_qk, cn_v = (cn, cn) if plan["ln1_ctx"] else _fp8_in(cn, at.add_q_proj, at.add_v_proj)
+        hn_qk, hn_v = (hn, hn) if plan["ln1"] else _fp8_in(hn, at.to_q, at.to_v)
         ops.linear_into(cn_qk, at.qk_packed(ctx=True), qk, 0, 0)
         ops.linear_into(hn_qk, at.qk_packed(), qk, Lc, 0)
         ops.linear_t_into(cn_v, at.add_v_proj.packed(), vt, 0)
@@ -162,8 +190,12 @@ class FluxTransformerBlock(nn.Module):
         o_out, o_add = _fp8_in(o, at.to_out[0], at.to_add_out)
         h = ops.linear_rows(o_out, Lc, Li, at.to_out[0].packed(), residual=h, gate=mi["g1"])
         c = ops.linear_rows(o_add, 0, Lc, at.to_add_out.packed(), residual=c, gate=mc["g1"])
-        h = self.ff.run(ops.layer_norm(h, mi["a2"], mi["b2"], 1e-6, split=self.ff.net[0].proj.in_split()), h, mi["g2"])
-        c = self.ff_context.run(ops.layer_norm(c, mc["a2"], mc["b2"], 1e-6, split=self.ff_context.net[0].proj.in_split()), c, mc["g2"])
+        hn2 = ops.layer_norm_mxfp8(h, mi["a2"], mi["b2"], 1e-6) if plan["ln2"] else \
+            ops.layer_norm(h, mi["a2"], mi["b2"], 1e-6, split=self.ff.net[0].proj.in_split())
+        h = self.ff.run(hn2, h, mi["g2"], hidden8=plan["ff"])
+        cn2 = ops.layer_norm_mxfp8(c, mc["a2"], mc["b2"], 1e-6) if plan["ln2_ctx"] else \
+            ops.layer_norm(c, mc["a2"], mc["b2"], 1e-6, split=self.ff_context.net[0].proj.in_split())
+        c = self.ff_context.run(cn2, c, mc["g2"], hidden8=plan["ffc"])
         return h, c
 
 
@@ -182,15 +214,24 @@ class FluxSingleTransformerBlock(nn.Module):
         shift, scale, gate = self.norm.fold(temb32)
         return dict(a=(1 + scale).contiguous(), b=shift, g=gate)
 
+    def quant_plan(self) -> dict:
+        """fused_quant_plan of this block (run() and the workspace allocation of FluxTransformer2DModel.tokens read the same answer)."""
+        at = self.attn
+        return fused_quant_plan(dict(to_q=at.to_q.fp8, to_v=at.to_v.fp8, proj_mlp=self.proj_mlp.fp8, proj_out=self.proj_out.fp8),
+                                dim=self.proj_mlp.in_features, hidden=self.mlp_hidden)
+
     def run(self, x, mod, rope, ws):
         """x [B, L, D] joint [text ; image] tokens (stream tensor): every GEMM sees M = B * L rows."""
         at = self.attn
         B, L, D = x.shape
-        xn = ops.layer_norm(x, mod["a"], mod["b"], 1e-6, split=at.to_q.in_split())      # read by to_q | to_k, to_v and proj_mlp
+        plan = self.quant_plan()
+        # read by to_q | to_k, to_v and proj_mlp
+        xn = ops.layer_norm_mxfp8(x, mod["a"], mod["b"], 1e-6) if plan["ln"] else ops.layer_norm(x, mod["a"], mod["b"], 1e-6, split=at.to_q.in_split())
         csp = self.proj_out.in_split()
-        qk, vt, cat = ws["qk"], ws["vt"], ws["cat2" if csp == 2 else "cat"]
+        # (cat8 blocks: the attention output is only quantised from, so it goes to the D-wide `o` buffer and no bf16 concat is touched)
+        qk, vt, cat = ws["qk"], ws["vt"], ws["o"] if plan["cat8"] else ws["cat2" if csp == 2 else "cat"]
         Kc = D + self.mlp_hidden                           # the [attn | mlp] operand of proj_out; split form: [hi (Kc) | lo (Kc)]
-        xn_qk, xn_v, xn_mlp = _fp8_in(xn, at.to_q, at.to_v, self.proj_mlp)
+        xn_qk, xn_v, xn_mlp = (xn, xn, xn) if plan["ln"] else _fp8_in(xn, at.to_q, at.to_v, self.proj_mlp)
         ops.linear_into(xn_qk.reshape(B * L, -1), at.qk_packed(), qk.reshape(B * L, -1), 0, 0, sample_rows=L)
         ops.linear_t_into(xn_v, at.to_v.packed(), vt, 0)
         if at.fp8:
@@ -201,6 +242,12 @@ class FluxSingleTransformerBlock(nn.Module):
             ops.rmsnorm_rope_(qk, at.norm_table(), rope[0], rope[1], 2 * at.heads, at.head_dim, pos0=0)
             ops.attention(qk, qk, vt, at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=L, out=cat,
                           out_split=csp, o_lo_col=Kc)
+        if plan["cat8"]:        # proj_out's MXFP8 operand built in place: proj_mlp's epilogue writes [D, Kc), the bf16 attention output goes into [0, D)
+            cat8 = ws["cat8"]
+            ops.linear_into(xn_mlp.reshape(B * L, -1), self.proj_mlp.packed(), None, 0, D, act=ops.ACT_GELU_TANH, sample_rows=L,
+                            out_mxfp8=cat8.reshape(B * L, -1))
+            ops.quantize_mxfp8(cat, out=cat8, out_col=0)
+            return self.proj_out.nhwc(cat8, residual=x, gate=mod["g"])
         cat2d = cat.reshape(B * L, -1)
         ops.linear_into(xn_mlp.reshape(B * L, -1), self.proj_mlp.packed(), cat2d, 0, D, act=ops.ACT_GELU_TANH, out_split=csp, lo_col0=Kc + D, sample_rows=L)
         return self.proj_out.nhwc(cat, residual=x, gate=mod["g"])
@@ -363,8 +410,10 @@ class FluxTransformer2DModel(ModelMixin, _Cached):
         ldv = ops._round_up(L, 128 if fp8_attn else 8)          # (the MXFP8 V^T: whole 128-key rows for the quantiser)
         ws = dict(qk=torch.empty((B, L, 2 * D), device=dev, dtype=ad),
                   vt=torch.empty((B, D, ldv), device=dev, dtype=ad),
-                  o=torch.empty((B, L, D), device=dev, dtype=ad),
-                  cat=torch.empty((B, L, D + mlp), device=dev, dtype=ad))
+                  o=torch.empty((B, L, D), device=dev, dtype=ad))
+        cat8_blocks = [b.quant_plan()["cat8"] for b in self.single_transformer_blocks]
+        if not all(cat8_blocks):        # the bf16 [attn | mlp] concat, for the single blocks that do not build proj_out's operand as MXFP8
+            ws["cat"] = torch.empty((B, L, D + mlp), device=dev, dtype=ad)
         if ops.precise():       # two-term split forms of the operands that to_out / to_add_out / proj_out read (policy dependent)
             if any(b.attn.to_out[0].in_split() == 2 for b in self.transformer_blocks):
                 ws["o2"] = torch.empty((B, L, 2 * D), device=dev, dtype=ad)
@@ -373,6 +422,8 @@ class FluxTransformer2DModel(ModelMixin, _Cached):
         if fp8_attn:            # the MXFP8 operands of the fp8 attention blocks: q | k from RMSNorm + RoPE, V^T from its quantiser
             ws["qk8"] = ops.Mxfp8(torch.empty((B, L, 2 * D), device=dev, dtype=torch.uint8), torch.empty((B, L, 2 * D // 32), device=dev, dtype=torch.uint8))
             ws["vt8"] = ops.Mxfp8(torch.empty((B, D, ldv), device=dev, dtype=torch.uint8), torch.empty((B, D, ldv // 32), device=dev, dtype=torch.uint8))
+        if any(cat8_blocks):    # the MXFP8 [attn | mlp] operand of proj_out where proj_mlp's epilogue writes the form
+            ws["cat8"] = ops.Mxfp8(torch.empty((B, L, D + mlp), device=dev, dtype=torch.uint8), torch.empty((B, L, (D + mlp) // 32), device=dev, dtype=torch.uint8))
         if ws["vt"].shape[-1] != L:
             ws["vt"].zero_()
         h = self.x_embedder.nhwc(x_tok)                                                   # [B, Li, D]

@@ -203,9 +203,10 @@ class Linear(nn.Linear, _Packed, _Operand):
         sp, wsp = self.in_split(), self.in_wsplit()
         return self._packed(lambda: ops.pack_linear_weight(self.weight, self.bias, split=sp, w_split=wsp), self.weight, self.bias, sp, wsp)
 
-    def nhwc(self, x, *, act=ops.ACT_NONE, residual=None, gate=None, out_dtype=ops.OUT_STREAM, gn_groups=0, out_split=1):
+    def nhwc(self, x, *, act=ops.ACT_NONE, residual=None, gate=None, out_dtype=ops.OUT_STREAM, gn_groups=0, out_split=1, out_mxfp8=None):
+        """out_mxfp8 (an fp8 layer only; True or an Mxfp8 to write into): the result as an Mxfp8, from the GEMM's epilogue (ops.linear)."""
         return ops.linear(x, self.packed(), act=act, residual=residual, gate=gate, out_dtype=out_dtype, gn_groups=gn_groups,
-                          out_split=out_split)
+                          out_split=out_split, out_mxfp8=out_mxfp8)
 
     def forward(self, x):
         y = self.nhwc(x.to(ops.stream_dtype()).contiguous())

@@ -521,25 +521,68 @@ def _mxfp8_like(x: torch.Tensor) -> Mxfp8:
                  torch.empty((*x.shape[:-1], x.shape[-1] // 32), device=x.device, dtype=torch.uint8))
 
 
-def quantize_mxfp8(x: torch.Tensor, out: Optional[Mxfp8] = None) -> Mxfp8:
+def parse_fp8_fused_quant(value: Optional[str]) -> dict:
+    """OMGSR_FP8_FUSED_QUANT -> which producers of the fp8 tier write their MXFP8 output themselves: unset = the measured defaults
+    below, "0" = none (the pass form everywhere: producer writes bf16, quantize_mxfp8 reads it), "1" = every fused producer. The fused forms
+    write the pass form's bytes, so the switch changes launches, never results."""
+    if value is None or value.strip() == "":
+        return dict(FP8_FUSED_QUANT_DEFAULT)
+    if value.strip() not in ("0", "1"):
+        raise ValueError(f"OMGSR_FP8_FUSED_QUANT must be 0 or 1, got {value!r}")
+    on = value.strip() == "1"
+    return {"layernorm": on, "gemm": on}
+
+
+# per fused producer kind. profiles/fp8_fused_quant.json: each kernel beats the launches it replaces; in the F-1024 batch-8 step the pair is the one
+# setting whose every step is faster than every pass-form step (each kind alone gains ~3 ms at the median, inside the spread) - so both are on
+FP8_FUSED_QUANT_DEFAULT = {"layernorm": True, "gemm": True}
+FP8_FUSED_QUANT = parse_fp8_fused_quant(os.environ.get("OMGSR_FP8_FUSED_QUANT"))         # A/B switch, parsed once at import
+
+
+def _row_pitch(x: torch.Tensor, name: str) -> int:
+    """Pitch (elements) of the rows of x [..., K]: x is dense, or the column window t[..., c0:c0 + K] of a dense tensor."""
+    K = x.shape[-1]
+    if x.dim() < 2 or x.is_contiguous():
+        return K
+    ld = x.stride(-2)
+    ok = x.stride(-1) == 1 and ld >= K and all(x.stride(i) == x.stride(i + 1) * x.shape[i + 1] for i in range(x.dim() - 2))
+    if not ok:
+        raise ValueError(f"{name}: expected a dense tensor or a column window of one")
+    return ld
+
+
+def quantize_mxfp8(x: torch.Tensor, out: Optional[Mxfp8] = None, out_col: Optional[int] = None) -> Mxfp8:
     """x bf16 or fp32 [..., K] (K % 128 == 0) -> its OMGSR_EL_MXFP8 form, on the device (omgsr_quantize_mxfp8): scale = max(0, biased
     exponent of the block's largest |v| - 8), code = (v / 2^(scale - 127)).clamp(-448, 448) in e4m3fn, round to nearest even.
-    out: a dense Mxfp8 of x's shape to write into (a workspace)."""
+    out: a dense Mxfp8 of x's shape to write into (a workspace).
+    out_col (with `out` a dense Mxfp8 [..., Kw], Kw >= K): x - dense, or a column window of a dense tensor - goes into columns
+    [out_col, out_col + K) of `out` (out_col % 128 == 0; omgsr_quantize_mxfp8_ld); the other columns are not touched. Returns `out`."""
     if x.dtype not in (torch.bfloat16, torch.float32):
         raise TypeError(f"quantize_mxfp8: expected bfloat16 or float32, got {x.dtype}")
-    _req(x, x.dtype, "x")
     K = x.shape[-1]
     if K % 128:
         raise ValueError(f"quantize_mxfp8: K = {K} is not a multiple of 128")
     rows = x.numel() // K
+    el = EL_F32 if x.dtype == torch.float32 else EL_16
+    if out_col is not None:
+        if out is None:
+            raise ValueError("quantize_mxfp8: out_col needs `out`")
+        Kw = out.codes.shape[-1]
+        if (out.codes.shape[:-1] != x.shape[:-1] or out.scales.shape != (*x.shape[:-1], Kw // 32) or Kw % 128 or out_col % 128 or out_col < 0
+                or out_col + K > Kw or not (out.codes.is_contiguous() and out.scales.is_contiguous())):
+            raise ValueError("quantize_mxfp8: x does not fit `out` at out_col")
+        check(_lib.load().omgsr_quantize_mxfp8_ld(x.data_ptr(), el, rows, K, _row_pitch(x, "quantize_mxfp8"), out.codes.data_ptr() + out_col,
+                                                  out.scales.data_ptr() + out_col // 32, Kw, Kw // 32, _stream()), "omgsr_quantize_mxfp8_ld")
+        return out
+    _req(x, x.dtype, "x")
     if out is not None:
         if out.codes.shape != x.shape or out.scales.shape != (*x.shape[:-1], K // 32) or not (out.codes.is_contiguous() and out.scales.is_contiguous()):
             raise ValueError("quantize_mxfp8: `out` does not match x")
         out = Mxfp8(out.codes, out.scales)
     else:
         out = _mxfp8_like(x)
-    check(_lib.load().omgsr_quantize_mxfp8(x.data_ptr(), EL_F32 if x.dtype == torch.float32 else EL_16, rows, K, K, out.codes.data_ptr(),
-                                           out.scales.data_ptr(), _stream()), "omgsr_quantize_mxfp8")
+    check(_lib.load().omgsr_quantize_mxfp8(x.data_ptr(), el, rows, K, K, out.codes.data_ptr(), out.scales.data_ptr(), _stream()),
+          "omgsr_quantize_mxfp8")
     return out
 
 
@@ -682,6 +725,46 @@ def _fill_out_slice(a: IgemmArgs, buf: torch.Tensor, first: int, *, ld: int = 0,
     a.out_ld, a.out_lo_off = ld, lo_off
     if t_rows is not None:
         a.out_layout, a.t_rows, a.t_ld = LAYOUT_T, t_rows, buf.shape[-1]
+
+
+def _fill_out_mxfp8(a: IgemmArgs, dst: Mxfp8, row0: int, col0: int) -> tuple:
+    """The output written as OMGSR_EL_MXFP8 (omgsr_igemm_out_mxfp8: the fp8 tier's MXFP8 GEMM only): rows row0 ..., columns col0 ... of the dense
+    planes of `dst` [rows, Kw] - the column offset goes into both pointers, the pitches are the planes' own. The code plane goes into the block;
+    returns what travels next to it: (scale pointer, scale pitch)."""
+    Kw = dst.codes.shape[-1]
+    a.out, a.out_dtype, a.out_ld = dst.codes.data_ptr() + row0 * Kw + col0, OUT_BF16, Kw
+    return dst.scales.data_ptr() + row0 * (Kw // 32) + col0 // 32, Kw // 32
+
+
+def _igemm_out_mxfp8(a: IgemmArgs, scale: tuple, what: str) -> None:
+    """Launch omgsr_igemm_out_mxfp8 (never splits K: no workspace)."""
+    check(_lib.load().omgsr_igemm_out_mxfp8(C.byref(a), scale[0], scale[1], _stream()), what)
+
+
+def _out_mxfp8_dst(what: str, out_mxfp8, pw: PackedWeight, lead, device, col0: int = 0, *, residual=None, gate=None, plain: bool = True) -> Optional[Mxfp8]:
+    """Validates an `out_mxfp8=` request (True: a fresh dense Mxfp8 [*lead, Cout]; an Mxfp8: the destination, dense, [*lead, Kw] with the
+    result at columns col0 ...) before anything is launched; None when not requested."""
+    if out_mxfp8 is None or out_mxfp8 is False:
+        return None
+    if not pw.fp8:
+        raise ValueError(f"{what}: out_mxfp8 needs an fp8-packed weight (the MXFP8 GEMM's epilogue writes the form)")
+    if residual is not None or gate is not None or not plain:
+        raise ValueError(f"{what}: out_mxfp8 goes with bias and act only (no residual, gate, GroupNorm statistics, split or fp32 output)")
+    if pw.cout % 32:
+        raise ValueError(f"{what}: out_mxfp8 needs Cout % 32 == 0, got {pw.cout}")
+    if out_mxfp8 is True:
+        if col0:
+            raise ValueError(f"{what}: out_mxfp8=True writes a dense result")
+        if pw.cout % 128:
+            raise ValueError(f"{what}: a dense Mxfp8 result needs Cout % 128 == 0, got {pw.cout}")
+        return Mxfp8(torch.empty((*lead, pw.cout), device=device, dtype=torch.uint8), torch.empty((*lead, pw.cout // 32), device=device, dtype=torch.uint8))
+    if not isinstance(out_mxfp8, Mxfp8):
+        raise TypeError(f"{what}: out_mxfp8 is True or an Mxfp8")
+    Kw = out_mxfp8.codes.shape[-1]
+    if (tuple(out_mxfp8.codes.shape[:-1]) != tuple(lead) or tuple(out_mxfp8.scales.shape) != (*lead, Kw // 32) or Kw % 128 or col0 % 128 or col0 < 0
+            or col0 + pw.cout > Kw or not (out_mxfp8.codes.is_contiguous() and out_mxfp8.scales.is_contiguous())):
+        raise ValueError(f"{what}: the result does not fit the Mxfp8 destination at column {col0}")
+    return out_mxfp8
 
 
 def _conv_args(a: IgemmArgs, x: torch.Tensor, pw: PackedWeight, stride, pad, upsample, act, residual, gate, out_dtype, alpha, out, out_split,
@@ -990,22 +1073,35 @@ def conv2d_multi(xs, pw: PackedWeight, *, stride: int = 1, pad: tuple[int, int, 
 
 def linear(x: torch.Tensor, pw: PackedWeight, *, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
            gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM, alpha: float = 1.0, gn_groups: int = 0,
-           out_split: int = 1) -> torch.Tensor:
+           out_split: int = 1, out_mxfp8=None):
     """x [..., K] -> [..., Cout]. gn_groups > 0 (x [B, ..., K]): the result feeds a GroupNorm over each x[b]; the GEMM
     then runs as B images of prod(...) rows so its epilogue can leave the per-image statistics (see conv2d).
-    An fp8-packed weight (pack_linear_weight_mxfp8) takes an Mxfp8 operand, or quantises a bf16 `x` first."""
+    An fp8-packed weight (pack_linear_weight_mxfp8) takes an Mxfp8 operand, or quantises a bf16 `x` first.
+    out_mxfp8 (fp8-packed weight only; True or a dense Mxfp8 [..., Cout] to write into): the result act(x W^T + bias) as an Mxfp8 - the bytes
+    of quantize_mxfp8(linear(..., out_dtype=OUT_BF16)), written by the GEMM's epilogue. No residual, gate, statistics or split."""
+    if out_mxfp8 is not None and out_mxfp8 is not False:
+        lead8 = (x.codes if isinstance(x, Mxfp8) else x).shape[:-1]
+        dst8 = _out_mxfp8_dst("linear", out_mxfp8, pw, lead8, (x.codes if isinstance(x, Mxfp8) else x).device, residual=residual, gate=gate,
+                              plain=not gn_groups and out_split == 1 and out_dtype in (OUT_STREAM, OUT_BF16) and alpha == 1.0)
+    else:
+        dst8 = None
     xq = _fp8_operand(x, pw, "linear")
     if xq is not None:
         if gn_groups or out_split != 1:
             raise ValueError("linear: an fp8 layer writes a plain output (no GroupNorm statistics, no split)")
         lead = xq.codes.shape[:-1]
         M = xq.codes.numel() // pw.cin
-        out = _out_tensor(lead, pw.cout, out_dtype, 1, xq.codes.device)
-        if residual is not None and residual.numel() != M * pw.cout:
-            raise ValueError("linear: residual must be [..., Cout]")
         a = IgemmArgs()
         _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)       # (not _fill_weight: this form never took the contraction-geometry fields)
         _fill_gemm(a, M)
+        if dst8 is not None:
+            scale = _fill_out_mxfp8(a, dst8.reshape(M, -1), 0, 0)
+            a.act, a.alpha, a.sample_rows = act, 1.0, M
+            _igemm_out_mxfp8(a, scale, "omgsr_igemm_out_mxfp8(linear)")
+            return dst8
+        out = _out_tensor(lead, pw.cout, out_dtype, 1, xq.codes.device)
+        if residual is not None and residual.numel() != M * pw.cout:
+            raise ValueError("linear: residual must be [..., Cout]")
         _fill_out(a, out, 1, residual, pw.cout)
         a.gate, a.act, a.alpha, a.sample_rows = _ptr(gate), act, alpha, M
         _igemm(a, out.device, "omgsr_igemm(linear, mxfp8)", workspace=False)
@@ -1034,11 +1130,30 @@ def carry_gn(src: torch.Tensor, view: torch.Tensor) -> torch.Tensor:
 
 def linear_into(x: torch.Tensor, pw: PackedWeight, out: torch.Tensor, row0: int, col0: int, *, act: int = ACT_NONE,
                 residual: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None, out_split: int = 1,
-                lo_col0: Optional[int] = None, sample_rows: int = 0) -> None:
+                lo_col0: Optional[int] = None, sample_rows: int = 0, out_mxfp8: Optional[Mxfp8] = None) -> None:
     """out[row0:row0+M, col0:col0+Cout] = epilogue(x @ W^T): writes a projection straight into a slice of a
     larger 2-D operand buffer `out` [rows, ld] (joint text+image sequences, [attn | mlp] concat). out_split 2: the low
     halves of the two-term split go to columns lo_col0 ... lo_col0+Cout of the same rows (default col0 + Cout).
-    An fp8-packed weight takes an Mxfp8 operand (or quantises `x`)."""
+    An fp8-packed weight takes an Mxfp8 operand (or quantises `x`).
+    out_mxfp8 (fp8-packed weight only; `out` is then None): a dense Mxfp8 [rows, Kw] - the result goes into its rows row0 ..., columns col0 ...
+    (col0 % 128 == 0) with the bytes quantize_mxfp8 makes of the bf16 slice; bias and act only."""
+    if out_mxfp8 is not None:
+        if out is not None:
+            raise ValueError("linear_into: either `out` or out_mxfp8")
+        if not isinstance(out_mxfp8, Mxfp8) or out_mxfp8.codes.dim() != 2:
+            raise TypeError("linear_into: out_mxfp8 is a dense Mxfp8 [rows, Kw]")
+        _out_mxfp8_dst("linear_into", out_mxfp8, pw, out_mxfp8.codes.shape[:-1], None, col0, residual=residual, gate=gate, plain=out_split == 1)
+        xq = _fp8_operand(x, pw, "linear_into")
+        M = xq.codes.numel() // pw.cin
+        if row0 < 0 or row0 + M > out_mxfp8.codes.shape[0]:
+            raise ValueError("linear_into: slice does not fit")
+        a = IgemmArgs()
+        _fill_weight(a, pw, xq.codes.data_ptr(), xq.scales.data_ptr())
+        _fill_gemm(a, M)
+        scale = _fill_out_mxfp8(a, out_mxfp8, row0, col0)
+        a.act, a.alpha, a.sample_rows = act, 1.0, sample_rows or M
+        _igemm_out_mxfp8(a, scale, "omgsr_igemm_out_mxfp8(linear_into)")
+        return
     xq = _fp8_operand(x, pw, "linear_into")
     if xq is not None:
         if out_split != 1:
@@ -1475,6 +1590,24 @@ def layer_norm(x: torch.Tensor, a: Optional[torch.Tensor], b: Optional[torch.Ten
     check(_lib.load().omgsr_layernorm(x.data_ptr(), y.data_ptr(), _ptr(a), _ptr(b), rows, Cc, eps, xel, _el_of_split(split), _stream()),
           "omgsr_layernorm")
     return y
+
+
+def layer_norm_mxfp8(x: torch.Tensor, a: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float, out: Optional[Mxfp8] = None) -> Mxfp8:
+    """bf16 stream tensor rows [..., C] (the fp8 tier; C % 128 == 0, C <= 4096) -> the normalised rows as an Mxfp8, written by the LayerNorm
+    kernel itself (omgsr_layernorm_mxfp8): the bytes of quantize_mxfp8(layer_norm(x, a, b, eps)). out: a dense Mxfp8 of x's shape."""
+    if x.dtype != torch.bfloat16 or _ACT != torch.bfloat16 or _PRECISE:
+        raise ValueError("layer_norm_mxfp8: a bf16 stream tensor under the bf16 compute type (the fp8 tier)")
+    _req(x, torch.bfloat16, "x")
+    Cc = x.shape[-1]
+    if Cc % 128 or Cc > 4096:
+        raise ValueError(f"layer_norm_mxfp8: C = {Cc} must be a multiple of 128, at most 4096")
+    if out is None:
+        out = _mxfp8_like(x)
+    elif out.codes.shape != x.shape or out.scales.shape != (*x.shape[:-1], Cc // 32) or not (out.codes.is_contiguous() and out.scales.is_contiguous()):
+        raise ValueError("layer_norm_mxfp8: `out` does not match x")
+    check(_lib.load().omgsr_layernorm_mxfp8(x.data_ptr(), _ptr(a), _ptr(b), x.numel() // Cc, Cc, eps, EL_16, out.codes.data_ptr(), out.scales.data_ptr(),
+                                            Cc, Cc // 32, _stream()), "omgsr_layernorm_mxfp8")
+    return out
 
 
 # --------------------------------------------------------------------------------------------

@@ -100,6 +100,20 @@ def mxfp8_ref(x: torch.Tensor):
     return q.reshape(x.shape), s.to(torch.uint8)
 
 
+def layer_norm_mxfp8_ref(x: torch.Tensor, a: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float):
+    """Reference of ops.layer_norm_mxfp8 (omgsr_layernorm_mxfp8): mxfp8_ref of the LayerNorm (x - mean) rstd a + b computed in fp32 (two-pass
+    variance, as the kernel) and rounded to bf16. x [..., C] (C % 32 == 0), a / b fp32 [C] or None -> (codes, scales)."""
+    xf = x.float()
+    mu = xf.mean(-1, keepdim=True)
+    d = xf - mu
+    y = d * torch.rsqrt((d * d).mean(-1, keepdim=True) + eps)
+    if a is not None:
+        y = y * a.float()
+    if b is not None:
+        y = y + b.float()
+    return mxfp8_ref(y.to(torch.bfloat16))
+
+
 def mxfp8_dequant(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     """The values an MXFP8 (codes, scales) pair stands for, in float64 (exact)."""
     lut = torch.arange(256, dtype=torch.int32).to(torch.uint8).view(torch.float8_e4m3fn).double().to(codes.device)
