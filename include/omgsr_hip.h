@@ -196,6 +196,18 @@ typedef struct omgsr_igemm_args {
  * a->out 16-byte aligned. Residual, gate, GroupNorm statistics, out_lo_off, LAYOUT_T and a problem that is not mxf8 return OMGSR_E_SHAPE
  * (never another kernel). Rows >= M and columns >= Cout are not written. Timing: kind OMGSR_TK_IGEMM, variant 18. */
 int omgsr_igemm_out_mxfp8(const omgsr_igemm_args* a, void* out_scale, int64_t out_scale_ld, void* stream);
+/* Additive under ABI v22 (no struct changed): `count` independent mxf8 problems through mxfp8_gemm_multi_kernel, at most 4 per launch (a
+ * larger `count` runs as successive launches of at most 4, in the order given; a group of one launches mxfp8_gemm_kernel, variant 18). Each
+ * problem keeps its own M, K, N, tensors, weight, bias, act, gate, residual, output kind (bf16 / fp32 / OMGSR_LAYOUT_T), out_ld and strides;
+ * the problems of a call share `batch` (grid.z) and the compute type. The result of every problem is, bit for bit, what its own omgsr_igemm
+ * call writes: a tile's bits do not depend on the launch it rides in. What it is for: pairs of small and large launches that together fit the
+ * rounds of 256-tile-per-CU workgroups the large one pays anyway (the fp8 tier's image / text projections of a FLUX double block).
+ * omgsr_igemm_mxfp8_multi_ok: 1 when every problem is one omgsr_igemm would run on mxfp8_gemm_kernel (mxf8 = 1, K % 128 == 0,
+ * Cout_pad % 256 == 0, out_mx = 0 - the OMGSR_EL_MXFP8 output form of omgsr_igemm_out_mxfp8 is not grouped - and the other rules of that
+ * kernel) and all problems agree in `batch`. omgsr_igemm_mxfp8_multi returns OMGSR_E_SHAPE for anything _multi_ok refuses (never another
+ * kernel; nothing is launched or written). Timing: kind OMGSR_TK_IGEMM, variant 24, one entry per launch with the summed flops and bytes. */
+int32_t omgsr_igemm_mxfp8_multi_ok(const omgsr_igemm_args* args, int32_t count);
+int omgsr_igemm_mxfp8_multi(const omgsr_igemm_args* args, int32_t count, void* stream);
 /* 1 when omgsr_igemm / omgsr_igemm_multi would run these arguments with the GroupNorm apply fused into the conv's patch producer (the
  * fields above may still be unset: the answer depends on geometry, operand / weight form, compute type and `in_el` only; for a problem of a
  * launch group call omgsr_igemm_multi_plan first). 0: run omgsr_groupnorm_apply and hand the conv its operand as before. */
@@ -558,7 +570,8 @@ int omgsr_timing_reset(void);
  * OMGSR_EL_MX operand), 10 / 11 igemm_halo_kernel / igemm_halo_multi_kernel with the GroupNorm apply fused into the patch producer, 12 the halo
  * kernel's split-K (chunk ranges as one igemm_halo_multi_kernel launch + splitk_reduce_kernel), 13 / 14 / 15 the halo kernel with fp6
  * (OMGSR_EL_MX6) correction chunks: single, launch group, split-K, 16 / 17 the same in the phase-decomposed form: single, launch group,
- * 18 mxfp8_gemm_kernel (ABI v18), 21 mxfp8_conv_kernel (ABI v22), 22 mxfp8_conv_multi_kernel (several problems of one layer in one launch).
+ * 18 mxfp8_gemm_kernel (ABI v18), 21 mxfp8_conv_kernel (ABI v22), 22 mxfp8_conv_multi_kernel (several problems of one layer in one launch),
+ * 24 mxfp8_gemm_multi_kernel (up to 4 independent MXFP8 GEMMs in one launch: omgsr_igemm_mxfp8_multi).
  * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19), 20 vae_attn_kernel (ABI v20, D = 512), 23 vae_attn_full_kernel (D = 512, every operand a two-term split). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;

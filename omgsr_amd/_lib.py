@@ -89,6 +89,8 @@ SIGNATURES = {
     "omgsr_error_string": (C.c_char_p, [C.c_int]),
     "omgsr_igemm": (C.c_int, [C.POINTER(IgemmArgs), _P]),
     "omgsr_igemm_out_mxfp8": (C.c_int, [C.POINTER(IgemmArgs), _P, _L, _P]),
+    "omgsr_igemm_mxfp8_multi_ok": (C.c_int32, [C.POINTER(IgemmArgs), _I]),
+    "omgsr_igemm_mxfp8_multi": (C.c_int, [C.POINTER(IgemmArgs), _I, _P]),
     "omgsr_igemm_multi_plan": (C.c_int, [C.POINTER(IgemmArgs), _I]),
     "omgsr_igemm_multi": (C.c_int, [C.POINTER(IgemmArgs), _I, _P]),
     "omgsr_set_batch_invariant": (C.c_int, [C.c_int]),

@@ -16,7 +16,9 @@
 
 namespace {
 
-__global__ __launch_bounds__(512, 2) void mxfp8_gemm_kernel(const omgsr_igemm_args p, const IgemmGeo g) { mxfp8_gemm_body<false>(p, g); }
+__global__ __launch_bounds__(512, 2) void mxfp8_gemm_kernel(const omgsr_igemm_args p, const IgemmGeo g) {
+    mxfp8_gemm_body<false>(p, g, xcd_remap(blockIdx.x, g.ntm * g.ntn), blockIdx.z);
+}
 
 // ---- quantiser: one thread per 32-element block ----------------------------------------------------------------------------
 template <typename TI>

@@ -46,8 +46,10 @@ OMGSR_DEVINL void glds4(const unsigned voff, const void* sbase, const unsigned l
         : "memory");
 }
 
+// `tile`: the workgroup's tile index in the problem's ntm x ntn grid (after xcd_remap), `bz`: its batch index. The single-problem kernels pass
+// xcd_remap(blockIdx.x, ...) and blockIdx.z; mxfp8_gemm_multi_kernel (gemm_mxfp8_multi.hip) passes what its lookup found.
 template <bool OUT8>
-OMGSR_DEVINL void mxfp8_gemm_body(const omgsr_igemm_args& p, const IgemmGeo& g, const IgemmOut8 o8 = IgemmOut8{nullptr, 0}) {
+OMGSR_DEVINL void mxfp8_gemm_body(const omgsr_igemm_args& p, const IgemmGeo& g, const int tile, const int bz, const IgemmOut8 o8 = IgemmOut8{nullptr, 0}) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     typedef int i32x4_t __attribute__((ext_vector_type(4)));
     const int t = threadIdx.x, lane = t & 63;
@@ -55,14 +57,12 @@ OMGSR_DEVINL void mxfp8_gemm_body(const omgsr_igemm_args& p, const IgemmGeo& g, 
     const int wr = wave >> 2, wc = wave & 3;
     const int half = lane >> 5, l31 = lane & 31;
 
-    const int tile = xcd_remap(blockIdx.x, g.ntm * g.ntn);
     const int per_group = 8 * g.ntn;
     const int grp = tile / per_group, in_grp = tile - grp * per_group;
     const int first_m = grp * 8;
     const int gsz = (g.ntm - first_m) < 8 ? (g.ntm - first_m) : 8;
     const int tm = first_m + in_grp % gsz, tn = in_grp / gsz;
     const int m0 = tm * BM, n0 = tn * BN;
-    const int bz = blockIdx.z;
     const int K = p.Cin;
     const int ksc = K >> 5;                             // scale bytes per row
     const unsigned char* abase = reinterpret_cast<const unsigned char*>(p.in) + (int64_t)bz * p.in_bstride;

@@ -6,7 +6,9 @@
 #include "gemm_mxfp8_body.hip.h"
 
 namespace {
-__global__ __launch_bounds__(512, 2) void mxfp8_gemm_out8_kernel(const omgsr_igemm_args p, const IgemmGeo g, const IgemmOut8 o8) { mxfp8_gemm_body<true>(p, g, o8); }
+__global__ __launch_bounds__(512, 2) void mxfp8_gemm_out8_kernel(const omgsr_igemm_args p, const IgemmGeo g, const IgemmOut8 o8) {
+    mxfp8_gemm_body<true>(p, g, xcd_remap(blockIdx.x, g.ntm * g.ntn), blockIdx.z, o8);
+}
 }  // namespace
 
 namespace omgsr {

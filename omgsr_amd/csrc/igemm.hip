@@ -36,6 +36,7 @@ int igemm_gmx_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
 bool mxfp8_gemm_ok(const omgsr_igemm_args& a);                                 // gemm_mxfp8.hip: OMGSR_EL_MXFP8 operand and weight
 int mxfp8_gemm_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
 int mxfp8_gemm_out8_launch(const omgsr_igemm_args& a, IgemmGeo g, unsigned char* out_scale, int64_t out_scale_ld, hipStream_t st);   // gemm_mxfp8_out8.hip
+int mxfp8_gemm_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int count, hipStream_t st, double flops, double bytes);   // gemm_mxfp8_multi.hip
 int igemm_halo_tiles(const omgsr_igemm_args& a, bool phase = false);
 bool igemm_halo_out6_ok(const omgsr_igemm_args& a);   // igemm_halo_out6.hip: the instantiations whose epilogue writes OMGSR_EL_MX6 can run this problem
 int igemm_halo_flat(const omgsr_igemm_args& a);      // pitch of the FLAT form the halo kernel would use for this problem (narrow maps), 0 = spatial tiles
@@ -795,6 +796,54 @@ extern "C" int omgsr_igemm_out_mxfp8(const omgsr_igemm_args* ap, void* out_scale
     omgsr::TimingScope ts(OMGSR_TK_IGEMM, flops, bytes, st, M64 * a.batch, a.Cout, (long long)a.Cin);
     ts.rec.variant = 18;                           // the same kernel body as the 16-bit form
     return omgsr::mxfp8_gemm_out8_launch(a, g, (unsigned char*)out_scale, out_scale_ld > 0 ? out_scale_ld : a.Cout / 32, st);
+}
+
+// ---- additive under ABI v22: up to 4 independent MXFP8 token GEMMs per launch through mxfp8_gemm_multi_kernel ----------------------------
+namespace {
+constexpr int MXG_MULTI_MAX = 4;                // problems per launch (gemm_mxfp8_multi.hip)
+// every member is a problem omgsr_igemm would hand to mxfp8_gemm_kernel (validate_args: mxfp8_gemm_ok; out_mx = 0, so no OUT8 form), and the
+// members agree in what a launch shares: grid.z
+bool igemm_mxfp8_multi_ok(const omgsr_igemm_args* args, const int count) {
+    if (!args || count <= 0) return false;
+    for (int i = 0; i < count; ++i) {
+        omgsr_igemm_args a = args[i];
+        if (a.mxf8 != 1 || a.batch != args[0].batch || validate_args(a) != 0) return false;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int32_t omgsr_igemm_mxfp8_multi_ok(const omgsr_igemm_args* args, int32_t count) { return igemm_mxfp8_multi_ok(args, count) ? 1 : 0; }
+
+extern "C" int omgsr_igemm_mxfp8_multi(const omgsr_igemm_args* args, int32_t count, void* stream) {
+    if (!args || count <= 0) return OMGSR_E_BADARG;
+    if (!igemm_mxfp8_multi_ok(args, count)) return OMGSR_E_SHAPE;       // every member is checked before the first launch
+    hipStream_t st = (hipStream_t)stream;
+    for (int at = 0; at < count; at += MXG_MULTI_MAX) {
+        const int ng = count - at < MXG_MULTI_MAX ? count - at : MXG_MULTI_MAX;
+        omgsr_igemm_args grp[MXG_MULTI_MAX];
+        Geo geo[MXG_MULTI_MAX];
+        double gf = 0.0, gb = 0.0;
+        for (int i = 0; i < ng; ++i) {
+            grp[i] = args[at + i];
+            validate_args(grp[i]);                      // (normalises in_ld)
+            grp[i].workspace = nullptr;
+            double f, b;
+            work_of(grp[i], &f, &b);
+            gf += f; gb += b;
+            geo[i] = geo_of(grp[i]);
+        }
+        int rc;
+        if (ng == 1) {                                  // a group of one is omgsr_igemm's launch
+            omgsr::TimingScope ts(OMGSR_TK_IGEMM, gf, gb, st, (long long)geo[0].M * grp[0].batch, grp[0].Cout, (long long)grp[0].Cin);
+            ts.rec.variant = 18;
+            rc = omgsr::mxfp8_gemm_launch(grp[0], geo[0], st);
+        } else {
+            rc = omgsr::mxfp8_gemm_launch_multi(grp, geo, ng, st, gf, gb);
+        }
+        if (rc != 0) return rc;
+    }
+    return 0;
 }
 
 extern "C" int omgsr_igemm(const omgsr_igemm_args* ap, void* stream) {

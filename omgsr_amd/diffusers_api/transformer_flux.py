@@ -22,6 +22,7 @@ slots; the double-stream blocks' projections into / out of the joint [text ; ima
 """
 from __future__ import annotations
 
+from contextlib import nullcontext
 from types import SimpleNamespace
 from typing import Optional
 
@@ -118,11 +119,13 @@ class FluxFeedForward(nn.Module):
 
     def run(self, xn, residual, gate, hidden8: bool = False):
         """hidden8 (fused_quant_plan: net[0].proj and net[2] are both fp8): the GELU hidden leaves net[0].proj's epilogue as an Mxfp8."""
+        return self.net[2].nhwc(self.hidden(xn, hidden8), residual=residual, gate=gate)
+
+    def hidden(self, xn, hidden8: bool = False):
+        """net[0].proj + GELU: the operand of net[2]."""
         if hidden8:
-            h = self.net[0].proj.nhwc(xn, act=ops.ACT_GELU_TANH, out_mxfp8=True)
-        else:
-            h = self.net[0].proj.nhwc(xn, act=ops.ACT_GELU_TANH, out_dtype=ops.OUT_BF16, out_split=self.net[2].in_split())
-        return self.net[2].nhwc(h, residual=residual, gate=gate)
+            return self.net[0].proj.nhwc(xn, act=ops.ACT_GELU_TANH, out_mxfp8=True)
+        return self.net[0].proj.nhwc(xn, act=ops.ACT_GELU_TANH, out_dtype=ops.OUT_BF16, out_split=self.net[2].in_split())
 
 
 class AdaLayerNormZero(nn.Module):
@@ -149,6 +152,7 @@ class FluxTransformerBlock(nn.Module):
         self.ff = FluxFeedForward(dim)
         self.norm2_context = LayerNorm(dim, elementwise_affine=False, eps=1e-6)
         self.ff_context = FluxFeedForward(dim)
+        self.gemm_groups = False    # the fp8 tier's opt-in paired launch groups (OMGSR_F_Infer.enable_gemm_groups)
 
     def fold(self, temb32):
         def six(norm):
@@ -174,10 +178,23 @@ class FluxTransformerBlock(nn.Module):
         # (fp8 tier: each LayerNorm output is quantised once - by the LayerNorm itself where the plan says so)
         cn_qk, cn_v = (cn, cn) if plan["ln1_ctx"] else _fp8_in(cn, at.add_q_proj, at.add_v_proj)
         hn_qk, hn_v = (hn, hn) if plan["ln1"] else _fp8_in(hn, at.to_q, at.to_v)
-        ops.linear_into(cn_qk, at.qk_packed(ctx=True), qk, 0, 0)
-        ops.linear_into(hn_qk, at.qk_packed(), qk, Lc, 0)
-        ops.linear_t_into(cn_v, at.add_v_proj.packed(), vt, 0)
-        ops.linear_t_into(hn_v, at.to_v.packed(), vt, Lc)
+        # gemm_groups (the fp8 tier, opt-in): the image launch and the text launch of a projection as ONE launch group (ops.gemm_group, image
+        # first) where both layers are fp8 - the text stream's few tiles ride in the rounds the image stream pays for. Same bits.
+        grp = self.gemm_groups
+        if grp and at.to_q.fp8 and at.add_q_proj.fp8:
+            with ops.gemm_group():
+                ops.linear_into(hn_qk, at.qk_packed(), qk, Lc, 0)
+                ops.linear_into(cn_qk, at.qk_packed(ctx=True), qk, 0, 0)
+        else:
+            ops.linear_into(cn_qk, at.qk_packed(ctx=True), qk, 0, 0)
+            ops.linear_into(hn_qk, at.qk_packed(), qk, Lc, 0)
+        if grp and at.to_v.fp8 and at.add_v_proj.fp8:
+            with ops.gemm_group():
+                ops.linear_t_into(hn_v, at.to_v.packed(), vt, Lc)
+                ops.linear_t_into(cn_v, at.add_v_proj.packed(), vt, 0)
+        else:
+            ops.linear_t_into(cn_v, at.add_v_proj.packed(), vt, 0)
+            ops.linear_t_into(hn_v, at.to_v.packed(), vt, Lc)
         cos, sin = rope
         if at.fp8:              # MXFP8 q | k straight out of RMSNorm + RoPE, V^T quantised once along the key index
             qk8 = ops.rmsnorm_rope_mxfp8(qk, at.norm_table(ctx=True), cos, sin, 2 * at.heads, at.head_dim, pos0=0, w_after=at.norm_table(),
@@ -188,8 +205,20 @@ class FluxTransformerBlock(nn.Module):
             ops.rmsnorm_rope_(qk, at.norm_table(ctx=True), cos, sin, 2 * at.heads, at.head_dim, pos0=0, w_after=at.norm_table(), split_at=Lc)
             ops.attention(qk, qk, vt, at.heads, at.head_dim, at.scale, q_col=0, k_col=at.inner, Lk=Lc + Li, out=o, out_split=osp)
         o_out, o_add = _fp8_in(o, at.to_out[0], at.to_add_out)
-        h = ops.linear_rows(o_out, Lc, Li, at.to_out[0].packed(), residual=h, gate=mi["g1"])
-        c = ops.linear_rows(o_add, 0, Lc, at.to_add_out.packed(), residual=c, gate=mc["g1"])
+        with (ops.gemm_group() if grp and at.to_out[0].fp8 and at.to_add_out.fp8 else nullcontext()):
+            h = ops.linear_rows(o_out, Lc, Li, at.to_out[0].packed(), residual=h, gate=mi["g1"])
+            c = ops.linear_rows(o_add, 0, Lc, at.to_add_out.packed(), residual=c, gate=mc["g1"])
+        if grp and self.ff.net[2].fp8 and self.ff_context.net[2].fp8:
+            # both LayerNorms and both net[0].proj first (independent work only moves), then the two net[2] as one group
+            hn2 = ops.layer_norm_mxfp8(h, mi["a2"], mi["b2"], 1e-6) if plan["ln2"] else \
+                ops.layer_norm(h, mi["a2"], mi["b2"], 1e-6, split=self.ff.net[0].proj.in_split())
+            cn2 = ops.layer_norm_mxfp8(c, mc["a2"], mc["b2"], 1e-6) if plan["ln2_ctx"] else \
+                ops.layer_norm(c, mc["a2"], mc["b2"], 1e-6, split=self.ff_context.net[0].proj.in_split())
+            hh, ch = self.ff.hidden(hn2, plan["ff"]), self.ff_context.hidden(cn2, plan["ffc"])
+            with ops.gemm_group():      # (a bf16 hidden is quantised at once by ops.linear: only the two GEMMs are deferred)
+                h = self.ff.net[2].nhwc(hh, residual=h, gate=mi["g2"])
+                c = self.ff_context.net[2].nhwc(ch, residual=c, gate=mc["g2"])
+            return h, c
         hn2 = ops.layer_norm_mxfp8(h, mi["a2"], mi["b2"], 1e-6) if plan["ln2"] else \
             ops.layer_norm(h, mi["a2"], mi["b2"], 1e-6, split=self.ff.net[0].proj.in_split())
         h = self.ff.run(hn2, h, mi["g2"], hidden8=plan["ff"])

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
 
@@ -234,13 +235,67 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-def _igemm(a: "IgemmArgs", device, what: str, z_batched_api: bool = False, workspace: bool = True) -> None:
+class _GemmGroup:
+    """What an ops.gemm_group scope collects: the argument blocks in call order, their labels, and the tensors they point into."""
+
+    def __init__(self):
+        self.blocks, self.whats, self.keep = [], [], []
+
+    def add(self, a: "IgemmArgs", what: str, keep=()) -> None:
+        self.blocks.append(a)
+        self.whats.append(what)
+        self.keep.append(tuple(keep))
+
+    def launch(self) -> None:
+        n = len(self.blocks)
+        if n == 0:
+            return
+        lib = _lib.load()
+        arr = (IgemmArgs * n)(*self.blocks)
+        if lib.omgsr_igemm_mxfp8_multi_ok(arr, n):
+            check(lib.omgsr_igemm_mxfp8_multi(arr, n, _stream()), "omgsr_igemm_mxfp8_multi(" + ", ".join(self.whats) + ")")
+        else:                                       # refused as a group: exactly the single calls, in order
+            for a, what in zip(self.blocks, self.whats):
+                check(lib.omgsr_igemm(C.byref(a), _stream()), what)
+        self.keep.clear()
+
+
+_GEMM_GROUP: Optional[_GemmGroup] = None
+
+
+@contextmanager
+def gemm_group():
+    """Deferred-launch scope of the fp8 tier's MXFP8 token GEMMs: inside it the plain MXFP8 forms of linear, linear_into, linear_rows and
+    linear_t_into (everything that reaches omgsr_igemm with mxf8 = 1) append their finished argument block instead of launching, and a clean
+    exit runs them as ONE omgsr_igemm_mxfp8_multi call in the order given (mxfp8_gemm_multi_kernel: up to 4 problems per launch, each
+    problem's bits those of its own launch). A group the library refuses (omgsr_igemm_mxfp8_multi_ok: differing grid.z, ...) runs as the
+    single calls it would have been. The outputs are allocated and returned at once but NOT written before the scope ends: only
+    independent work belongs inside. OUT8 calls (out_mxfp8=) and problems that are not mxf8 launch immediately, as outside a scope. An
+    exception inside the scope launches nothing; scopes do not nest."""
+    global _GEMM_GROUP
+    if _GEMM_GROUP is not None:
+        raise RuntimeError("ops.gemm_group: scopes do not nest")
+    grp = _GEMM_GROUP = _GemmGroup()
+    try:
+        yield grp
+    except BaseException:
+        _GEMM_GROUP = None
+        raise
+    _GEMM_GROUP = None
+    grp.launch()
+
+
+def _igemm(a: "IgemmArgs", device, what: str, z_batched_api: bool = False, workspace: bool = True, keep=()) -> None:
     """Launch omgsr_igemm; when the library wants to split K (small-M / long-K problems) hand it an fp32 scratch.
     z_batched_api: the caller puts the images of a call on grid.z and offers a workspace (linear_into is the one that does). The library
     cannot split K there when there is more than one image, so in batch-invariant mode it must not split the one-image call either
     (round 4: OMGSR-F batch 1 == batch N bit for bit under ops.set_batch_invariant).
     workspace=False: no query and a NULL workspace, so the library never splits K (linear_rows, linear_t_into, linear_t, bmm_nt and the
-    fp8 form of linear)."""
+    fp8 form of linear).
+    keep: the tensors the block points into, held by an open ops.gemm_group scope until it launches."""
+    if _GEMM_GROUP is not None and a.mxf8 == 1:     # ops.gemm_group: the finished block joins the scope (an mxf8 problem never splits K)
+        _GEMM_GROUP.add(a, what, keep)
+        return
     lib = _lib.load()
     need = 0 if (not workspace or (z_batched_api and _BATCH_INVARIANT)) else lib.omgsr_igemm_workspace_bytes(C.byref(a))
     ws = None
@@ -1104,7 +1159,7 @@ def linear(x: torch.Tensor, pw: PackedWeight, *, act: int = ACT_NONE, residual: 
             raise ValueError("linear: residual must be [..., Cout]")
         _fill_out(a, out, 1, residual, pw.cout)
         a.gate, a.act, a.alpha, a.sample_rows = _ptr(gate), act, alpha, M
-        _igemm(a, out.device, "omgsr_igemm(linear, mxfp8)", workspace=False)
+        _igemm(a, out.device, "omgsr_igemm(linear, mxfp8)", workspace=False, keep=(xq, pw, out, residual, gate))
         return out
     lead = x.shape[:-1]
     M = 1
@@ -1185,7 +1240,7 @@ def linear_into(x: torch.Tensor, pw: PackedWeight, out: torch.Tensor, row0: int,
         a.residual, a.res_el = residual.data_ptr(), _el(residual, "residual")
     a.gate, a.act, a.alpha = _ptr(gate), act, 1.0
     a.sample_rows = sample_rows or M              # rows of ONE image when the caller flattened a batch into M (batch-invariant dispatch)
-    _igemm(a, x.device, "omgsr_igemm(linear_into)", z_batched_api=True)
+    _igemm(a, x.device, "omgsr_igemm(linear_into)", z_batched_api=True, keep=(x, xq, pw, out, residual, gate))
 
 
 def linear_rows(x_buf: torch.Tensor, row0: int, rows: int, pw: PackedWeight, *, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
@@ -1212,7 +1267,7 @@ def linear_rows(x_buf: torch.Tensor, row0: int, rows: int, pw: PackedWeight, *, 
     _fill_gemm(a, rows, B, L * K, 0, rows * pw.cout)
     _fill_out(a, out, 1, residual, pw.cout)
     a.gate, a.act, a.alpha, a.sample_rows = _ptr(gate), act, 1.0, rows
-    _igemm(a, x_buf.device, "omgsr_igemm(linear_rows)", workspace=False)
+    _igemm(a, x_buf.device, "omgsr_igemm(linear_rows)", workspace=False, keep=(x_buf, xq, pw, out, residual, gate))
     return out
 
 
@@ -1237,7 +1292,7 @@ def linear_t_into(x: torch.Tensor, pw: PackedWeight, out_t: torch.Tensor, key0: 
     _fill_gemm(a, L, Bz, L * K, 0, pw.cout * out_t.shape[-1])
     _fill_out_slice(a, out_t, key0, t_rows=L)
     a.alpha, a.sample_rows = 1.0, L
-    _igemm(a, x.device, "omgsr_igemm(linear_t_into)", workspace=False)
+    _igemm(a, x.device, "omgsr_igemm(linear_t_into)", workspace=False, keep=(x, xq, pw, out_t))
 
 
 def linear_t(x: torch.Tensor, pw: PackedWeight, rows_per_batch: int, ld: Optional[int] = None) -> torch.Tensor:

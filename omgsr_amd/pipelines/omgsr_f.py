@@ -115,6 +115,23 @@ class OMGSR_F_Infer(torch.nn.Module):
         self.graphs.enabled = os.environ.get("OMGSR_GRAPH", "0") == "1"
         self.range_fallback.on_mode_change = self.graphs.clear
         self._graph_params = None
+        # (the switch names the fp8 tier: other tiers ignore it; a transformer handed in by the caller may carry another pipeline's setting)
+        self._set_gemm_groups(fp8 and os.environ.get("OMGSR_FP8_GEMM_GROUPS", "0") == "1")
+
+    def _set_gemm_groups(self, on: bool) -> None:
+        self.gemm_groups = bool(on)
+        for blk in self.flux_transformer.transformer_blocks:
+            blk.gemm_groups = self.gemm_groups
+
+    def enable_gemm_groups(self, on: bool = True) -> None:
+        """fp8 tier, opt-in (OMGSR_FP8_GEMM_GROUPS=1): every double block runs the image and the text launch of its q|k, V^T, to_out /
+        to_add_out and net[2] projections as one launch group (ops.gemm_group, mxfp8_gemm_multi_kernel) where both layers are fp8. The image
+        is the same bit for bit; what changes is the number of launches (4 groups instead of 8 launches per double block). Off: not one
+        launch changes. Captured hipGraphs are dropped on a change."""
+        if not self.fp8:
+            raise ValueError("enable_gemm_groups: the paired launch groups belong to the fp8 tier (weight_dtype=torch.float8_e4m3fn)")
+        self.graphs.clear()
+        self._set_gemm_groups(on)
 
     def enable_graphs(self, on: bool = True) -> None:
         """See OMGSR_S_Infer.enable_graphs."""
@@ -203,7 +220,7 @@ class OMGSR_F_Infer(torch.nn.Module):
             if not self.graphs.enabled:
                 return body(lq_img)
             hooks = (id(getattr(self.vae.encoder, "_tile_hook", None)), id(getattr(self.vae.decoder, "_tile_hook", None)))
-            key = ("F", tile_size, tile_overlap, float(self.t_curr), float(self.guidance_scale), hooks, self._weights_stamp())
+            key = ("F", tile_size, tile_overlap, float(self.t_curr), float(self.guidance_scale), hooks, self._weights_stamp(), self.gemm_groups)
             return self.graphs.call(key, [lq_img], [prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, self.vae.posterior_noise], body)
         # FLUX activations are why the reference defaults to bf16: when an fp16 operand leaves the fp16 range the call runs again with
         # bf16 operands and the pipeline STAYS range-safe (precision.RangeFallback), instead of paying two passes and two re-packs per image

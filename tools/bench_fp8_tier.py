@@ -14,6 +14,12 @@
       GEMM kind alone, both - alternated rounds in one process, plus the per-kind launch table of one step per arm;
   (c) the same step on the parent commit's build: --parent-json takes the file this tool wrote when run WITHOUT --fused-quant (--no-gemm) from a
       checkout of that commit in the same visit to the machine; its fp8 arm is recorded as `parent_commit_step`.
+
+--gemm-groups [--batch 1,2,8] measures the fp8 tier's paired launch groups (writes profiles/fp8_gemm_groups.json):
+  (a) the four image / text pairs of a double block at batch 1 (4096 and 512 tokens), two launches against one ops.gemm_group;
+  (b) the F-1024 full-depth step of the fp8 tier at each batch, groups off and on in alternated rounds in one process, HIP events;
+  (c) the same step on the parent commit's build: --parent-json takes the file this tool wrote with --gemm-groups --parent-arm (the step as
+      the checkout it runs from builds it, no switch touched) from a checkout of that commit in the same visit to the machine.
 """
 from __future__ import annotations
 
@@ -231,6 +237,88 @@ def fused_quant_step(dev, rounds: int, steps: int) -> dict:
     return out
 
 
+GROUP_PAIRS = {"to_q|k": (3072, 6144), "to_v": (3072, 3072), "to_out/to_add_out": (3072, 3072), "ff.net.2": (12288, 3072)}      # (K, N)
+
+
+def gemm_group_pairs(dev) -> dict:
+    """(a): per pair at batch 1, the image launch (4096 rows) + the text launch (512 rows) against the two as one launch group."""
+    import torch
+    from omgsr_amd import ops
+    out = {}
+    for name, (K, N) in GROUP_PAIRS.items():
+        g = torch.Generator(device=dev).manual_seed(K + N)
+        mk = lambda rows: ops.quantize_mxfp8(torch.randn(rows, K, generator=g, device=dev).to(torch.bfloat16))      # noqa: E731
+        pk = lambda: ops.pack_linear_weight_mxfp8((torch.randn(N, K, generator=g, device=dev) / K ** 0.5).to(torch.bfloat16), torch.zeros(N, device=dev))      # noqa: E731
+        xi, xt, wi, wt = mk(4096), mk(512), pk(), pk()
+
+        def pair(grouped):
+            if grouped:
+                with ops.gemm_group():
+                    ops.linear(xi, wi); ops.linear(xt, wt)
+            else:
+                ops.linear(xi, wi); ops.linear(xt, wt)
+        off = [_events_ms(lambda: pair(False), 50) for _ in range(3)]
+        on = [_events_ms(lambda: pair(True), 50) for _ in range(3)]
+        t_img, t_txt = _events_ms(lambda: ops.linear(xi, wi), 50), _events_ms(lambda: ops.linear(xt, wt), 50)
+        out[name] = dict(K=K, N=N, image_alone_ms=round(t_img, 4), text_alone_ms=round(t_txt, 4), two_launches_ms=[round(t, 4) for t in off],
+                         one_group_ms=[round(t, 4) for t in on], saved_ms_median=round(statistics.median(off) - statistics.median(on), 4))
+        print(name, json.dumps(out[name]), flush=True)
+        del xi, xt, wi, wt
+        torch.cuda.empty_cache()
+    return out
+
+
+def gemm_groups_step(dev, rounds: int, steps: int, batches, parent_arm: bool) -> dict:
+    """(b) / (c): the fp8 tier's F-1024 step per batch size. The blocks' `gemm_groups` attribute is what OMGSR_F_Infer.enable_gemm_groups sets;
+    parent_arm: one arm, nothing set (a checkout without the feature)."""
+    import torch
+    import bench
+    from omgsr_amd.precision import FLUX_FP8, set_fp8_linear
+    family, side, _, tile, overlap, _ = bench.WORKLOADS["f1024"]
+    pipe, _ = bench.build_f(dev, 0, 1, torch.bfloat16)
+    set_fp8_linear(pipe.flux_transformer, FLUX_FP8)
+    arms = ["parent"] if parent_arm else ["off", "on"]
+    out = {}
+    for B in batches:
+        inp = bench.make_inputs(family, side, B, tile, 0, dev, torch.bfloat16)
+        pipe.vae.posterior_noise = inp["eps"].to(dev)
+        step = bench.make_step(pipe, family, inp, tile, overlap)
+        times = {a: [] for a in arms}
+        with torch.no_grad():
+            for r in range(rounds):
+                for a in (arms if r % 2 == 0 else arms[::-1]):
+                    if not parent_arm:
+                        for blk in pipe.flux_transformer.transformer_blocks:
+                            blk.gemm_groups = a == "on"
+                    step(); step()
+                    torch.cuda.synchronize()
+                    for _ in range(steps):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        step()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        times[a].append(e0.elapsed_time(e1))
+                    print(f"batch {B} round {r} {a}: {[round(t, 2) for t in times[a][-steps:]]} ms", flush=True)
+            rec = {a: dict(median_ms=round(statistics.median(ts), 3), min_ms=round(min(ts), 3), max_ms=round(max(ts), 3),
+                           samples_ms=[round(t, 3) for t in ts]) for a, ts in times.items()}
+            if not parent_arm:
+                for blk in pipe.flux_transformer.transformer_blocks:
+                    blk.gemm_groups = True
+                step()
+                kinds = _kind_table(step)
+                rec["on_igemm_launches_one_step"] = {k: v for k, v in kinds.items() if k in ("igemm/18", "igemm/24")}
+                rec["saved_ms_median"] = round(rec["off"]["median_ms"] - rec["on"]["median_ms"], 3)
+                for blk in pipe.flux_transformer.transformer_blocks:
+                    blk.gemm_groups = False
+        out[f"batch_{B}"] = rec
+        print(f"batch {B}", json.dumps({a: {k: v for k, v in rec[a].items() if k != "samples_ms"} for a in arms}), flush=True)
+        del inp, step
+        torch.cuda.empty_cache()
+    out["shape"] = dict(workload="f1024", side=side, tile=tile, overlap=overlap, timer="HIP events around one step", rounds=rounds, steps=steps)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=3)
@@ -239,15 +327,45 @@ def main():
     ap.add_argument("--no-gemm", action="store_true")
     ap.add_argument("--fused-quant", action="store_true", help="measure the fused MXFP8 producers (see the module docstring)")
     ap.add_argument("--parent-json", default=None, help="--fused-quant: the parent commit's run of this tool (its fp8 step) to record as (c)")
+    ap.add_argument("--gemm-groups", action="store_true", help="measure the paired launch groups (see the module docstring)")
+    ap.add_argument("--batch", default="1,2,8", help="--gemm-groups: batch sizes of the step, comma-separated")
+    ap.add_argument("--parent-arm", action="store_true", help="--gemm-groups: the step as this checkout builds it, one arm (the parent commit's run)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "fp8_fused_quant.json" if args.fused_quant else "fp8_tier.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "fp8_gemm_groups.json" if args.gemm_groups else
+                                        "fp8_fused_quant.json" if args.fused_quant else "fp8_tier.json")
     import torch
     from omgsr_amd import _lib, ops
     dev = torch.device("cuda", 0)
     _lib.check(_lib.load().omgsr_check_device(), "omgsr_check_device")
     ops.set_compute_dtype(torch.bfloat16)
     rec = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__)
+    if args.gemm_groups:
+        batches = [int(b) for b in args.batch.split(",")]
+        if not args.no_gemm and not args.parent_arm:
+            rec["pairs_batch_1"] = gemm_group_pairs(dev)
+        if not args.no_step:
+            rec["f1024_step"] = gemm_groups_step(dev, args.rounds, args.steps, batches, args.parent_arm)
+        if args.parent_json:
+            with open(args.parent_json) as f:
+                parent = json.load(f)["f1024_step"]
+            rec["parent_commit_step"] = dict({k: v["parent"] for k, v in parent.items() if k.startswith("batch_")},
+                                             note="the parent commit's own build and Python, run on the same machine in the same visit just before this process")
+            if "f1024_step" in rec:
+                cmp_ = {}
+                for k, v in rec["f1024_step"].items():
+                    if k.startswith("batch_") and k in parent:
+                        p = parent[k]["parent"]
+                        cmp_[k] = dict(off_median_minus_parent_ms=round(v["off"]["median_ms"] - p["median_ms"], 3),
+                                       on_median_minus_parent_ms=round(v["on"]["median_ms"] - p["median_ms"], 3),
+                                       every_grouped_step_faster_than_every_parent_step=v["on"]["max_ms"] < p["min_ms"],
+                                       parent_spread_ms=round(p["max_ms"] - p["min_ms"], 3))
+                rec["parent_commit_step"]["comparison"] = cmp_
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print(f"wrote {args.out}")
+        return
     if args.fused_quant:
         if not args.no_gemm:
             rec["kernels_alone"] = fused_quant_kernels(dev)
