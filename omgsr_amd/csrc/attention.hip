@@ -478,23 +478,13 @@ template <int D, bool DMA, bool SPLIT = false>
 int launch_attn(const omgsr_attn_args& a, hipStream_t st) {
     constexpr int KT = SPLIT ? 2 : 1;
     constexpr int LDS = DMA ? 2 * KT * (64 * 2 * D + D * 128) : 2 * KT * (64 * (2 * D + 16) + D * 136);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<bf16_t, D, DMA, SPLIT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kernel<f16_t, D, DMA, SPLIT>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     const int ntiles = (a.Lk + 63) / 64;
     const int qtiles = (a.Lq + 127) / 128;
     const int64_t blocks = (int64_t)qtiles * a.H * a.B;
     if (blocks > 0x7fffffffll) return OMGSR_E_SHAPE;
     static const char* xo = getenv("OMGSR_ATTN_XCD");            // A/B runs: "0" = natural block order (every XCD reads every head's K / V^T)
     const int xcd_order = !(xo && xo[0] == '0');
-    OMGSR_DISPATCH_T(hipLaunchKernelGGL((attn_kernel<T, D, DMA, SPLIT>), dim3((unsigned)blocks), dim3(256), LDS, st, a, ntiles, g_defer_max, qtiles, xcd_order));
-    return (int)hipGetLastError();
+    OMGSR_DISPATCH_T(return launch_lds<attn_kernel<T, D, DMA, SPLIT>>(dim3((unsigned)blocks), dim3(256), LDS, st, a, ntiles, g_defer_max, qtiles, xcd_order));
 }
 
 }  // namespace

@@ -320,13 +320,6 @@ template <int NCH, bool SPLIT, bool FULL = false>
 int launch_vae_attn(const omgsr_attn_args& a, hipStream_t st, const float defer) {
     constexpr int LDS = 2 * ((SPLIT ? 2 : 1) * K_BYTES + (FULL ? 2 : 1) * NCH * VP);
     static_assert(LDS <= 160 * 1024, "two stages must fit the LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vae_attn_fn<bf16_t, NCH, SPLIT, FULL>()), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(vae_attn_fn<f16_t, NCH, SPLIT, FULL>()), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     // every choice below depends on one sample's Lq / Lk only (batch-invariant by construction)
     const int ntiles = (a.Lk + KT - 1) / KT;
     const int qtiles = (a.Lq + 127) / 128;
@@ -334,8 +327,7 @@ int launch_vae_attn(const omgsr_attn_args& a, hipStream_t st, const float defer)
     if (blocks > 0x7fffffffll) return OMGSR_E_SHAPE;
     static const char* xo = getenv("OMGSR_ATTN_XCD");            // A/B runs: "0" = natural block order
     const int xcd_order = !(xo && xo[0] == '0');
-    OMGSR_DISPATCH_T(hipLaunchKernelGGL((vae_attn_fn<T, NCH, SPLIT, FULL>()), dim3((unsigned)blocks), dim3(256), LDS, st, a, ntiles, defer, qtiles, xcd_order));
-    return (int)hipGetLastError();
+    OMGSR_DISPATCH_T(return launch_lds<vae_attn_fn<T, NCH, SPLIT, FULL>()>(dim3((unsigned)blocks), dim3(256), LDS, st, a, ntiles, defer, qtiles, xcd_order));
 }
 
 }  // namespace

@@ -335,12 +335,6 @@ int mxfp8_attention(const omgsr_attn_args& a, hipStream_t st) {
         return OMGSR_E_SHAPE;
     // 32-bit DMA offsets: (Lk - 1) k_ld + 128 and 127 vt_ld + 64 from the SGPR bases
     if ((int64_t)a.Lk * a.k_ld >= (1ll << 31) || 128ll * a.vt_ld >= (1ll << 31)) return OMGSR_E_SHAPE;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mxfp8_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     const int ntiles = (a.Lk + KT - 1) / KT;
     const int qtiles = (a.Lq + 127) / 128;
     const int64_t blocks = (int64_t)qtiles * a.H * a.B;
@@ -349,7 +343,6 @@ int mxfp8_attention(const omgsr_attn_args& a, hipStream_t st) {
     const double bytes = (double)a.B * a.H * a.D * (33.0 / 32.0 * (a.Lq + 2.0 * a.Lk) + 2.0 * a.Lq);
     TimingScope ts(OMGSR_TK_ATTN, flops, bytes, st, (long long)a.B * a.H * a.Lq, a.Lk, a.D);
     if (ts.active) ts.rec.variant = 19;
-    hipLaunchKernelGGL(mxfp8_attn_kernel, dim3((unsigned)blocks), dim3(256), LDS_BYTES, st, a, ntiles, qtiles);
-    return (int)hipGetLastError();
+    return launch_lds<mxfp8_attn_kernel>(dim3((unsigned)blocks), dim3(256), LDS_BYTES, st, a, ntiles, qtiles);
 }
 }  // namespace omgsr

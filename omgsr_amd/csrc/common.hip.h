@@ -291,3 +291,19 @@ static inline const char* ablation_env(const char* name) {
     const char* ok = getenv("OMGSR_ABLATION_OK");
     return (ok && ok[0] == '1') ? getenv(name) : nullptr;
 }
+
+// Launch of a kernel that asks for more than 64 KB of dynamic LDS (every hot-path kernel does): such a kernel must be opted in with
+// hipFuncAttributeMaxDynamicSharedMemorySize before its first launch. K is the kernel itself, so the opt-in and the launch cannot name
+// different instantiations; the flag is per K (an instantiation is opted in at ITS first launch: pipelines/graphed.py runs every key eagerly
+// before it captures, which is where that happens). Returns the hipError_t of a failed opt-in (nothing is launched) or of the launch.
+template <auto K, typename... A>
+int launch_lds(const dim3 grid, const dim3 block, const int lds_bytes, hipStream_t st, const A&... args) {
+    static bool opted_in = false;
+    if (!opted_in) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return (int)e;
+        opted_in = true;
+    }
+    hipLaunchKernelGGL(K, grid, block, lds_bytes, st, args...);
+    return (int)hipGetLastError();
+}

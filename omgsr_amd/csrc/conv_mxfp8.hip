@@ -295,50 +295,29 @@ bool mxfp8_conv_shape_ok(const omgsr_igemm_args& a) {
 int mxfp8_conv_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, const double flops) {
     const bool narrow = halo_geo(a, g, false);
     if (narrow || g.flat) return OMGSR_E_SHAPE;               // (omgsr_conv_mxfp8_ok refused both: never reached)
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mxfp8_conv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MXC_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     const double M = (double)a.N * a.Ho * a.Wo;
     const double bytes = (1.0 + 1.0 / 32.0) * ((double)a.N * a.H * a.W * a.Cin + (double)a.Cout_pad * a.K_pad) +
                          M * a.Cout * ((a.out_dtype == OMGSR_OUT_F32 ? 4.0 : 2.0) + (a.residual ? (a.res_el == OMGSR_EL_F32 ? 4.0 : 2.0) : 0.0));
     TimingScope ts(OMGSR_TK_IGEMM, flops, bytes, st, (long long)M, a.Cout, 9ll * a.Cin);
     if (ts.active) ts.rec.variant = 21;
-    hipLaunchKernelGGL(mxfp8_conv_kernel, dim3(g.ntm * g.ntn), dim3(256), MXC_LDS_BYTES, st, a, g);
-    return (int)hipGetLastError();
+    return launch_lds<mxfp8_conv_kernel>(dim3(g.ntm * g.ntn), dim3(256), MXC_LDS_BYTES, st, a, g);
 }
 
 // `count` problems (2 ... HALO_MULTI_MAX) that omgsr_conv_mxfp8_multi_ok accepted as one group, in one launch of mxfp8_conv_multi_kernel
 int mxfp8_conv_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, const int count, hipStream_t st, const double flops) {
     if (count < 2 || count > HALO_MULTI_MAX) return OMGSR_E_BADARG;
     HaloMulti m{};
-    m.count = count;
-    int at = 0;
+    const HaloPack k = halo_multi_pack(a, g0, count, false, m);
+    if (k.narrow || k.flat) return OMGSR_E_SHAPE;             // (omgsr_conv_mxfp8_multi_ok refused both: never reached)
     double M = 0.0, bytes = (1.0 + 1.0 / 32.0) * (double)a[0].Cout_pad * a[0].K_pad;
     for (int i = 0; i < count; ++i) {
-        m.p[i] = a[i];
-        m.g[i] = g0[i];
-        const bool narrow = halo_geo(a[i], m.g[i], false);
-        if (narrow || m.g[i].flat) return OMGSR_E_SHAPE;      // (omgsr_conv_mxfp8_multi_ok refused both: never reached)
-        m.start[i] = at;
-        at += (m.g[i].ntm * m.g[i].ntn + 7) & ~7;
         const double Mi = (double)a[i].N * a[i].Ho * a[i].Wo;
         M += Mi;
         bytes += (1.0 + 1.0 / 32.0) * (double)a[i].N * a[i].H * a[i].W * a[i].Cin +
                  Mi * a[i].Cout * ((a[i].out_dtype == OMGSR_OUT_F32 ? 4.0 : 2.0) + (a[i].residual ? (a[i].res_el == OMGSR_EL_F32 ? 4.0 : 2.0) : 0.0));
     }
-    m.start[count] = at;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mxfp8_conv_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MXC_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     TimingScope ts(OMGSR_TK_IGEMM, flops, bytes, st, (long long)M, a[0].Cout, 9ll * a[0].Cin);
     if (ts.active) ts.rec.variant = 22;
-    hipLaunchKernelGGL(mxfp8_conv_multi_kernel, dim3(at), dim3(256), MXC_LDS_BYTES, st, m);
-    return (int)hipGetLastError();
+    return launch_lds<mxfp8_conv_multi_kernel>(dim3(k.blocks), dim3(256), MXC_LDS_BYTES, st, m);
 }
 }  // namespace omgsr

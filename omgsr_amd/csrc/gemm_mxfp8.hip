@@ -85,14 +85,7 @@ int mxfp8_gemm_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st) {
     g.ntm = (g.M + BM - 1) / BM;
     g.ntn = (a.Cout + BN - 1) / BN;
     g.splits = 1;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mxfp8_gemm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(mxfp8_gemm_kernel, dim3(g.ntm * g.ntn, 1, a.batch), dim3(512), LDS_BYTES, st, a, g);
-    return (int)hipGetLastError();
+    return launch_lds<mxfp8_gemm_kernel>(dim3(g.ntm * g.ntn, 1, a.batch), dim3(512), LDS_BYTES, st, a, g);
 }
 }  // namespace omgsr
 

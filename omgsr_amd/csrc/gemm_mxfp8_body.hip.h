@@ -6,6 +6,7 @@
 #include "../../include/omgsr_hip.h"
 #include "timing.hip.h"
 #include "igemm_epilogue.hip.h"
+#include "igemm_launch.hip.h"
 #include "mxfp8.hip.h"
 #include <type_traits>
 

@@ -51,15 +51,8 @@ int mxfp8_gemm_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, const
         rows += (long long)m.g[i].M * a[i].batch;
     }
     for (int i = count; i <= MXG_MULTI_MAX; ++i) m.start[i] = at;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mxfp8_gemm_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     TimingScope ts(OMGSR_TK_IGEMM, flops, bytes, st, rows, a[0].Cout, (long long)a[0].Cin);
     if (ts.active) ts.rec.variant = 24;
-    hipLaunchKernelGGL(mxfp8_gemm_multi_kernel, dim3(at, 1, a[0].batch), dim3(512), LDS_BYTES, st, m);
-    return (int)hipGetLastError();
+    return launch_lds<mxfp8_gemm_multi_kernel>(dim3(at, 1, a[0].batch), dim3(512), LDS_BYTES, st, m);
 }
 }  // namespace omgsr

@@ -20,30 +20,10 @@
 #include "../../include/omgsr_hip.h"
 #include "timing.hip.h"
 #include "igemm_epilogue.hip.h"
+#include "igemm_launch.hip.h"
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
-
-namespace omgsr {
-int igemm_dma_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
-int igemm_halo_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, bool phase = false);
-int igemm_halo_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int count, hipStream_t st, bool phase);
-int igemm_halo_launch_splitk(const omgsr_igemm_args& a, const IgemmGeo& g0, int splits, hipStream_t st);     // igemm_halo_multi.hip
-bool igemm_p8_wanted(const omgsr_igemm_args& a, const IgemmGeo& g);
-int igemm_p8_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
-bool igemm_gmx_ok(const omgsr_igemm_args& a);
-int igemm_gmx_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
-bool mxfp8_gemm_ok(const omgsr_igemm_args& a);                                 // gemm_mxfp8.hip: OMGSR_EL_MXFP8 operand and weight
-int mxfp8_gemm_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
-int mxfp8_gemm_out8_launch(const omgsr_igemm_args& a, IgemmGeo g, unsigned char* out_scale, int64_t out_scale_ld, hipStream_t st);   // gemm_mxfp8_out8.hip
-int mxfp8_gemm_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int count, hipStream_t st, double flops, double bytes);   // gemm_mxfp8_multi.hip
-int igemm_halo_tiles(const omgsr_igemm_args& a, bool phase = false);
-bool igemm_halo_out6_ok(const omgsr_igemm_args& a);   // igemm_halo_out6.hip: the instantiations whose epilogue writes OMGSR_EL_MX6 can run this problem
-int igemm_halo_flat(const omgsr_igemm_args& a);      // pitch of the FLAT form the halo kernel would use for this problem (narrow maps), 0 = spatial tiles
-int igemm_halo_tiles_form(const omgsr_igemm_args& a, int flat);
-int igemm_halo_gn_slots(const omgsr_igemm_args& a, bool phase = false);
-bool igemm_halo_gn_geometry_ok(const omgsr_igemm_args& a);     // igemm_halo_gn.hip: what the normalising patch producer can run
-}
 
 namespace omgsr { static int g_batch_invariant = 0; }
 extern "C" int omgsr_set_batch_invariant(int on) { omgsr::g_batch_invariant = (on != 0); return 0; }
@@ -667,11 +647,6 @@ extern "C" int omgsr_igemm_multi(const omgsr_igemm_args* args, int32_t count, vo
 }
 
 // ---- ABI v22: MXFP8 x MXFP8 3x3 convolution (conv_mxfp8.hip) -----------------------------------------------------------------------
-namespace omgsr {
-bool mxfp8_conv_shape_ok(const omgsr_igemm_args& a);
-int mxfp8_conv_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, double flops);
-int mxfp8_conv_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int count, hipStream_t st, double flops);
-}
 namespace {
 // Served: what mxfp8_conv_kernel runs AND the geometry for which this dispatcher hands the bf16 problem to the halo-tile kernel's spatial
 // nine-tap form (tile-count policy included, one sample's rows in batch-invariant mode): the fp8 form replaces that launch, nothing else

@@ -24,6 +24,7 @@
 #include "common.hip.h"
 #include "../../include/omgsr_hip.h"
 #include "igemm_epilogue.hip.h"
+#include "igemm_launch.hip.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -276,18 +277,8 @@ int launch_dma(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st) {
     g.ntm = (g.M + BM - 1) / BM;
     const int logical_cols = (a.act == OMGSR_ACT_GEGLU) ? 2 * a.Cout : a.Cout;
     g.ntn = (logical_cols + WGN * WTN - 1) / (WGN * WTN);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_dma_kernel<bf16_t, WGM, WGN, ABL, BM>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(BM, WGN));
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_dma_kernel<f16_t, WGM, WGN, ABL, BM>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(BM, WGN));
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     dim3 grid(g.ntm * g.ntn, g.splits, a.batch);
-    OMGSR_DISPATCH_T(hipLaunchKernelGGL((igemm_dma_kernel<T, WGM, WGN, ABL, BM>), grid, dim3(WGM * WGN * 64), lds_bytes(BM, WGN), st, a, g));
-    return (int)hipGetLastError();
+    OMGSR_DISPATCH_T(return launch_lds<igemm_dma_kernel<T, WGM, WGN, ABL, BM>>(grid, dim3(WGM * WGN * 64), lds_bytes(BM, WGN), st, a, g));
 }
 
 }  // namespace

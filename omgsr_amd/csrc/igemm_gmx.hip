@@ -21,6 +21,7 @@
 #include "common.hip.h"
 #include "../../include/omgsr_hip.h"
 #include "igemm_epilogue.hip.h"
+#include "igemm_launch.hip.h"
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
@@ -231,20 +232,12 @@ int launch_gmx(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st) {
     g.ntm = (g.M + BM - 1) / BM;
     const int logical_cols = (a.act == OMGSR_ACT_GEGLU) ? 2 * a.Cout : a.Cout;
     g.ntn = (logical_cols + BN - 1) / BN;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_gmx_kernel<BM>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(BM));
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((igemm_gmx_kernel<BM>), dim3(g.ntm * g.ntn), dim3(256), lds_bytes(BM), st, a, g);
-    return (int)hipGetLastError();
+    return launch_lds<igemm_gmx_kernel<BM>>(dim3(g.ntm * g.ntn), dim3(256), lds_bytes(BM), st, a, g);
 }
 
 }  // namespace
 
 namespace omgsr {
-int compute_dtype();
 // GEMM-shaped problem over an OMGSR_EL_MX operand: 1x1, stride 1, no padding / upsampling, one batch entry, C % 64 == 0 logical channels
 // (Cin = 2C 16-bit slots), fp16 compute type, no wrap (the row carries its own fp8 copies)
 bool igemm_gmx_ok(const omgsr_igemm_args& a) {

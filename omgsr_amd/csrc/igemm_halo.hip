@@ -35,15 +35,7 @@ static int prio_min_cin() {
     return v;
 }
 
-int igemm_halo_launch_mx(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
-int igemm_halo_flat_launch(const omgsr_igemm_args& a, const IgemmGeo& g, hipStream_t st);       // igemm_halo_flat.hip
-int igemm_halo_launch_f16(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, bool phase, bool narrow);      // igemm_halo_f16.hip
-
 // one problem per grid, bf16 compute type (the fp16 instantiations are a translation unit of their own: hipcc compiles the files in parallel)
-int igemm_halo_gn_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);        // igemm_halo_gn.hip
-
-int igemm_halo_out6_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);              // igemm_halo_out6.hip
-
 int igemm_halo_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, const bool phase) {
     if (a.out_mx == 6) return phase ? OMGSR_E_SHAPE : igemm_halo_out6_launch(a, g, st);
     if (a.gn_scale_shift) return phase ? OMGSR_E_SHAPE : igemm_halo_gn_launch(a, g, st);
@@ -52,32 +44,18 @@ int igemm_halo_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, con
     if (g.flat) return igemm_halo_flat_launch(a, g, st);
     if (omgsr::compute_dtype() == 1) return igemm_halo_launch_f16(a, g, st, phase, narrow);
     using T = bf16_t;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[] = {reinterpret_cast<const void*>(igemm_halo_kernel<T, 0, false>),
-                             reinterpret_cast<const void*>(igemm_halo_kernel<T, 0, true>),
-                             reinterpret_cast<const void*>(igemm_halo_kernel<T, 1, false>),
-                             reinterpret_cast<const void*>(igemm_halo_kernel<T, 2, false>),
-                             reinterpret_cast<const void*>(igemm_halo_kernel<T, 3, false>),
-                             reinterpret_cast<const void*>(igemm_halo_kernel<T, 0, false, true>),
-                             reinterpret_cast<const void*>(igemm_halo_kernel<T, 5, false>),
-                             reinterpret_cast<const void*>(igemm_halo_kernel<T, 0, false, false, 4>)};
-        const int rc = halo_set_lds_attr(fns, (int)(sizeof(fns) / sizeof(fns[0])));
-        if (rc != 0) return rc;
-        attr_set = true;
-    }
-    const dim3 grid = (phase && g.interleave) ? dim3(32 * ((g.ntm * g.ntn + 7) / 8)) : dim3(g.ntm * g.ntn, phase ? 4 : 1, 1);
+    const dim3 grid = halo_grid(g, phase), block(256);
     static const char* abl = ablation_env("OMGSR_HALO_ABLATE");      // timing experiments only: results are garbage (needs OMGSR_ABLATION_OK=1; bf16 only)
     static const char* var = getenv("OMGSR_HALO_VARIANT");     // A/B runs: "0" = LDS-DMA issued in front of the step's MFMAs
-    if (phase) hipLaunchKernelGGL((igemm_halo_kernel<T, 0, false, false, 4>), grid, dim3(256), LDS_BYTES, st, a, g);
-    else if (var && var[0] == '0' && !narrow) hipLaunchKernelGGL((igemm_halo_kernel<T, 5, false>), grid, dim3(256), LDS_BYTES, st, a, g);
-    else if (abl && abl[0] == '1') hipLaunchKernelGGL((igemm_halo_kernel<T, 1, false>), grid, dim3(256), LDS_BYTES, st, a, g);
-    else if (abl && abl[0] == '2') hipLaunchKernelGGL((igemm_halo_kernel<T, 2, false>), grid, dim3(256), LDS_BYTES, st, a, g);
-    else if (abl && abl[0] == '3') hipLaunchKernelGGL((igemm_halo_kernel<T, 3, false>), grid, dim3(256), LDS_BYTES, st, a, g);
-    else if (narrow) hipLaunchKernelGGL((igemm_halo_kernel<T, 0, false, true>), grid, dim3(256), LDS_BYTES, st, a, g);
-    else if (a.Cin >= prio_min_cin()) hipLaunchKernelGGL((igemm_halo_kernel<T, 0, true>), grid, dim3(256), LDS_BYTES, st, a, g);
-    else hipLaunchKernelGGL((igemm_halo_kernel<T, 0, false>), grid, dim3(256), LDS_BYTES, st, a, g);
-    return (int)hipGetLastError();
+    // (the ablation, variant and priority instantiations exist as one-problem kernels only: named in full, <T, ABL, PRIO>)
+    if (phase) return launch_lds<halo_one<T, COLS_128, 4>>(grid, block, LDS_BYTES, st, a, g);
+    if (var && var[0] == '0' && !narrow) return launch_lds<igemm_halo_kernel<T, 5, false>>(grid, block, LDS_BYTES, st, a, g);
+    if (abl && abl[0] == '1') return launch_lds<igemm_halo_kernel<T, 1, false>>(grid, block, LDS_BYTES, st, a, g);
+    if (abl && abl[0] == '2') return launch_lds<igemm_halo_kernel<T, 2, false>>(grid, block, LDS_BYTES, st, a, g);
+    if (abl && abl[0] == '3') return launch_lds<igemm_halo_kernel<T, 3, false>>(grid, block, LDS_BYTES, st, a, g);
+    if (narrow) return launch_lds<halo_one<T, COLS_32, 9>>(grid, block, LDS_BYTES, st, a, g);
+    if (a.Cin >= prio_min_cin()) return launch_lds<igemm_halo_kernel<T, 0, true>>(grid, block, LDS_BYTES, st, a, g);
+    return launch_lds<halo_one<T, COLS_128, 9>>(grid, block, LDS_BYTES, st, a, g);
 }
 
 int igemm_halo_gn_slots(const omgsr_igemm_args& a, const bool phase) {

@@ -26,6 +26,7 @@
 #include "common.hip.h"
 #include "../../include/omgsr_hip.h"
 #include "igemm_epilogue.hip.h"
+#include "igemm_launch.hip.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -629,11 +630,80 @@ static inline bool halo_geo(const omgsr_igemm_args& a, IgemmGeo& g, const bool p
     g.ntn = narrow ? 1 : (logical_cols + BN - 1) / BN;
     return narrow;
 }
-static inline int halo_set_lds_attr(const void* const* fns, const int n, const int bytes = LDS_BYTES) {
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < n; ++i)
-        if (e == hipSuccess) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return (int)e;
+
+// ---- host side: how the translation units name, size and launch the instantiations ----------------------------------------------------
+// Names for the template arguments of igemm_halo_kernel / igemm_halo_multi_kernel (see halo_body)
+constexpr bool COLS_128 = false, COLS_32 = true;          // NARROW
+constexpr int MX_NONE = 0, MX_FP8 = 1, MX_FP6 = 6;        // MX: correction chunks
+constexpr int FLAT_OFF = 0, FLAT_22 = 1, FLAT_27 = 2;     // FLAT: spatial tiles, flattened map with the 22- / the 27-piece patch
+constexpr int GNF_OFF = 0, GNF_ON = 1;                    // GNF: GroupNorm apply as the patch producer
+constexpr bool OUT6_ON = true, SPLITK_ON = true;
+constexpr int FLAT_22_MAX_PITCH = 47;                     // 256 + 2 P + 2 patch rows <= 352 (22 pieces); a wider pitch takes the 27-piece patch
+
+// The shipped forms (ABL = 0, PRIO = false) of the one-problem kernel and of the group kernel, under ONE parameter order
+template <typename T, bool NARROW, int TAPS, int MX = MX_NONE, int FLAT = FLAT_OFF, int GNF = GNF_OFF, bool OUT6 = false>
+constexpr auto halo_one = &igemm_halo_kernel<T, 0, false, NARROW, TAPS, MX, FLAT, GNF, OUT6>;
+template <typename T, bool NARROW, int TAPS, int MX = MX_NONE, int FLAT = FLAT_OFF, int GNF = GNF_OFF, bool OUT6 = false>
+constexpr auto halo_group = &igemm_halo_multi_kernel<T, NARROW, TAPS, MX, FLAT, GNF, false, OUT6>;
+// dynamic LDS of a form: follows from its template arguments
+constexpr int halo_lds_bytes(const int flat, const int gnf) { return gnf ? LDS_BYTES_GN : flat == FLAT_27 ? LDS_BYTES_BIG : LDS_BYTES; }
+
+// Grids. Phase form (TAPS = 4): the interleaved block orders are x-only grids of 4 x the 8-aligned tile range, order 0 puts the phase in
+// blockIdx.y (see igemm_halo_kernel); every other form is one block per tile.
+static inline dim3 halo_grid(const IgemmGeo& g, const bool phase) {
+    return (phase && g.interleave) ? dim3(32 * ((g.ntm * g.ntn + 7) / 8)) : dim3(g.ntm * g.ntn, phase ? 4 : 1, 1);
+}
+// ... of a launch group: `blocks` = the 8-aligned block total of its prefix table, g0 = its first problem's geometry
+static inline dim3 halo_multi_grid(const IgemmGeo& g0, const unsigned blocks, const bool phase) {
+    return (phase && g0.interleave) ? dim3(4 * blocks) : dim3(blocks, phase ? 4 : 1, 1);
+}
+
+// Fills the table of a launch group from `count` argument blocks (<= HALO_MULTI_MAX): halo_geo of every problem, each problem's block range
+// starting on a multiple of 8. The problems of a group share Cout and their form (omgsr_igemm_multi groups them so), hence one pair of flags.
+struct HaloPack { int blocks; bool narrow, flat; };
+static inline HaloPack halo_multi_pack(const omgsr_igemm_args* a, const IgemmGeo* g0, const int count, const bool phase, HaloMulti& m) {
+    HaloPack k{0, false, false};
+    m.count = count;
+    for (int i = 0; i < count; ++i) {
+        m.p[i] = a[i];
+        m.g[i] = g0[i];
+        const bool narrow = halo_geo(a[i], m.g[i], phase);        // (a function of Cout and `phase` only: the same for every problem of a group)
+        k.narrow = k.narrow || narrow;
+        k.flat = k.flat || m.g[i].flat != 0;
+        m.start[i] = k.blocks;
+        k.blocks += (m.g[i].ntm * m.g[i].ntn + 7) & ~7;
+    }
+    m.start[count] = k.blocks;
+    return k;
+}
+
+// What a selection chain launches: one problem on a grid of its own, or a launch group. A unit that holds both kernels of a configuration
+// writes its chain once over a HaloJob; halo_run picks the kernel by which job it got. (Adding an instantiation = one more branch in the
+// unit's chain: launch_lds opts it in, halo_run sizes its LDS and grid.)
+struct HaloJob {
+    const omgsr_igemm_args* a; const IgemmGeo* g;       // one problem (m == nullptr), g after halo_geo
+    const HaloMulti* m; unsigned blocks;                // a launch group
+    hipStream_t st;
+};
+static inline HaloJob halo_job(const omgsr_igemm_args& a, const IgemmGeo& g, hipStream_t st) { return HaloJob{&a, &g, nullptr, 0u, st}; }
+// (the group launchers get their HaloMulti as an opaque pointer: igemm_launch.hip.h says why)
+static inline HaloJob halo_job(const void* halo_multi, const unsigned blocks, hipStream_t st) {
+    return HaloJob{nullptr, nullptr, reinterpret_cast<const HaloMulti*>(halo_multi), blocks, st};
+}
+template <typename T, bool NARROW, int TAPS, int MX = MX_NONE, int FLAT = FLAT_OFF, int GNF = GNF_OFF, bool OUT6 = false>
+int halo_run(const HaloJob& j) {
+    constexpr int lds = halo_lds_bytes(FLAT, GNF);
+    if (j.m) return launch_lds<halo_group<T, NARROW, TAPS, MX, FLAT, GNF, OUT6>>(halo_multi_grid(j.m->g[0], j.blocks, TAPS == 4), dim3(256), lds, j.st, *j.m);
+    return launch_lds<halo_one<T, NARROW, TAPS, MX, FLAT, GNF, OUT6>>(halo_grid(*j.g, TAPS == 4), dim3(256), lds, j.st, *j.a, *j.g);
+}
+// The correction-chunk units (igemm_halo_mx.hip: MX_FP8, igemm_halo_mx6.hip: MX_FP6) select alike: fp16 compute type, wide shape; the
+// up-sampling conv's phase form, a split-K group of chunk ranges of one problem (group kernel only), or the plain nine-tap form.
+template <int MX>
+int halo_mx_run(const HaloJob& j, const bool phase, const bool splitk) {
+    if (phase) return halo_run<f16_t, COLS_128, 4, MX>(j);
+    if (splitk && !j.m) return OMGSR_E_BADARG;              // (chunk ranges are the members of a launch group: a one-problem job never asks for them)
+    if (splitk) return launch_lds<igemm_halo_multi_kernel<f16_t, COLS_128, 9, MX, FLAT_OFF, GNF_OFF, SPLITK_ON>>(halo_multi_grid(j.m->g[0], j.blocks, false), dim3(256), LDS_BYTES, j.st, *j.m);
+    return halo_run<f16_t, COLS_128, 9, MX>(j);
 }
 
 }  // namespace

@@ -4,57 +4,25 @@
 #include "igemm_halo_body.hip.h"
 
 namespace omgsr {
-static int multi_attrs() {
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[] = {reinterpret_cast<const void*>(igemm_halo_multi_kernel<bf16_t, false, 9>),
-                             reinterpret_cast<const void*>(igemm_halo_multi_kernel<f16_t, false, 9>),
-                             reinterpret_cast<const void*>(igemm_halo_multi_kernel<bf16_t, true, 9>),
-                             reinterpret_cast<const void*>(igemm_halo_multi_kernel<f16_t, true, 9>),
-                             reinterpret_cast<const void*>(igemm_halo_multi_kernel<bf16_t, false, 4>),
-                             reinterpret_cast<const void*>(igemm_halo_multi_kernel<f16_t, false, 4>)};
-        const int rc = halo_set_lds_attr(fns, (int)(sizeof(fns) / sizeof(fns[0])));
-        if (rc != 0) return rc;
-        attr_set = true;
-    }
-    return 0;
-}
-
-int igemm_halo_launch_multi_mx(const void* halo_multi, unsigned blocks, hipStream_t st);
-int igemm_halo_gn_launch_multi(const void* halo_multi, unsigned blocks, bool narrow, hipStream_t st);      // igemm_halo_gn.hip
-int igemm_halo_out6_launch_multi(const void* halo_multi, unsigned blocks, hipStream_t st);                 // igemm_halo_out6.hip
-int igemm_halo_flat_launch_multi(const void* halo_multi, unsigned blocks, hipStream_t st);      // igemm_halo_flat.hip       // igemm_halo_mx.hip (HaloMulti has no linkage: same header, opaque pointer)
-
 // `count` problems (<= HALO_MULTI_MAX) in one launch; all of them take the same kernel shape (the caller checks: same weights,
 // Cin / Cout, epilogue options; `phase`, narrow-ness and the mixed-precision form therefore agree). The workgroup looks its problem up
 // in a prefix table of tile counts; each problem's range starts on a multiple of 8 blocks so the XCD remap of its local index keeps
 // its meaning (the filler blocks exit).
 int igemm_halo_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, const int count, hipStream_t st, const bool phase) {
     HaloMulti m;
-    m.count = count;
-    int at = 0;
-    bool narrow = false, flat = false;
-    for (int i = 0; i < count; ++i) {
-        m.p[i] = a[i];
-        m.g[i] = g0[i];
-        narrow = halo_geo(a[i], m.g[i], phase);
-        flat = flat || m.g[i].flat != 0;                 // (omgsr_igemm_multi groups problems by form: all of a launch's problems agree)
-        m.start[i] = at;
-        at += (m.g[i].ntm * m.g[i].ntn + 7) & ~7;
-    }
-    m.start[count] = at;
-    const int rc = multi_attrs();
-    if (rc != 0) return rc;
-    const dim3 grid = (phase && m.g[0].interleave) ? dim3(4 * at) : dim3(at, phase ? 4 : 1, 1);
+    const HaloPack k = halo_multi_pack(a, g0, count, phase, m);
+    const bool narrow = k.narrow, flat = k.flat;
+    const unsigned blocks = (unsigned)k.blocks;
     if (m.g[0].cc1 > 0 && (flat || phase || narrow || a[0].mx_chunks16 <= 0 || a[0].gn_scale_shift)) return OMGSR_E_SHAPE;      // split-K: the spatial MX instantiation only (halo_splitk_plan)
-    if (a[0].out_mx == 6) return (phase || flat || narrow || m.g[0].cc1 > 0) ? OMGSR_E_SHAPE : igemm_halo_out6_launch_multi(&m, (unsigned)at, st);
-    if (a[0].gn_scale_shift) return (phase || flat) ? OMGSR_E_SHAPE : igemm_halo_gn_launch_multi(&m, (unsigned)at, narrow, st);
-    if (flat) return igemm_halo_flat_launch_multi(&m, (unsigned)at, st);
-    if (a[0].mx_chunks16 > 0) return igemm_halo_launch_multi_mx(&m, (unsigned)at, st);
-    if (phase) OMGSR_DISPATCH_T(hipLaunchKernelGGL((igemm_halo_multi_kernel<T, false, 4>), grid, dim3(256), LDS_BYTES, st, m));
-    else if (narrow) OMGSR_DISPATCH_T(hipLaunchKernelGGL((igemm_halo_multi_kernel<T, true, 9>), grid, dim3(256), LDS_BYTES, st, m));
-    else OMGSR_DISPATCH_T(hipLaunchKernelGGL((igemm_halo_multi_kernel<T, false, 9>), grid, dim3(256), LDS_BYTES, st, m));
-    return (int)hipGetLastError();
+    if (a[0].out_mx == 6) return (phase || flat || narrow || m.g[0].cc1 > 0) ? OMGSR_E_SHAPE : igemm_halo_out6_launch_multi(&m, blocks, st);
+    if (a[0].gn_scale_shift) return (phase || flat) ? OMGSR_E_SHAPE : igemm_halo_gn_launch_multi(&m, blocks, narrow, st);
+    if (flat) return igemm_halo_flat_launch_multi(&m, blocks, st);
+    if (a[0].mx_chunks16 > 0) return igemm_halo_launch_multi_mx(&m, blocks, st);
+    // the plain 16-bit forms: group kernels of this unit (their one-problem kernels are igemm_halo.hip's and igemm_halo_f16.hip's)
+    const dim3 grid = halo_multi_grid(m.g[0], blocks, phase), block(256);
+    if (phase) OMGSR_DISPATCH_T(return launch_lds<halo_group<T, COLS_128, 4>>(grid, block, LDS_BYTES, st, m));
+    if (narrow) OMGSR_DISPATCH_T(return launch_lds<halo_group<T, COLS_32, 9>>(grid, block, LDS_BYTES, st, m));
+    OMGSR_DISPATCH_T(return launch_lds<halo_group<T, COLS_128, 9>>(grid, block, LDS_BYTES, st, m));
 }
 
 // Split-K (igemm.hip: halo_splitk_plan): `splits` chunk ranges of ONE problem as the members of a launch group. Each member is the problem itself with

@@ -6,18 +6,9 @@
 #include "igemm_halo_body.hip.h"
 
 namespace omgsr {
-static int out6_attrs() {
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[] = {reinterpret_cast<const void*>(igemm_halo_kernel<f16_t, 0, false, false, 9, 0, 0, 0, true>),
-                             reinterpret_cast<const void*>(igemm_halo_kernel<f16_t, 0, false, false, 9, 6, 0, 0, true>),
-                             reinterpret_cast<const void*>(igemm_halo_multi_kernel<f16_t, false, 9, 0, 0, 0, false, true>),
-                             reinterpret_cast<const void*>(igemm_halo_multi_kernel<f16_t, false, 9, 6, 0, 0, false, true>)};
-        const int rc = halo_set_lds_attr(fns, 4);
-        if (rc != 0) return rc;
-        attr_set = true;
-    }
-    return 0;
+// `mx6`: the operand carries fp6 correction chunks
+static int out6_run(const HaloJob& j, const bool mx6) {
+    return mx6 ? halo_run<f16_t, COLS_128, 9, MX_FP6, FLAT_OFF, GNF_OFF, OUT6_ON>(j) : halo_run<f16_t, COLS_128, 9, MX_NONE, FLAT_OFF, GNF_OFF, OUT6_ON>(j);
 }
 // what these instantiations can run (omgsr_igemm_out_mx6_ok: the host asks before it requests out_mx = 6)
 bool igemm_halo_out6_ok(const omgsr_igemm_args& a) {
@@ -25,20 +16,12 @@ bool igemm_halo_out6_ok(const omgsr_igemm_args& a) {
            (a.mx_chunks16 == 0 || a.mx_fmt == 6);          // (never FLAT: halo_flat_eligible() refuses out_mx = 6 problems)
 }
 int igemm_halo_out6_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st) {
-    const int rc = out6_attrs();
-    if (rc != 0) return rc;
     halo_geo(a, g, false);
     if (g.flat) return OMGSR_E_SHAPE;
-    if (a.mx_chunks16 > 0) hipLaunchKernelGGL((igemm_halo_kernel<f16_t, 0, false, false, 9, 6, 0, 0, true>), dim3(g.ntm * g.ntn), dim3(256), LDS_BYTES, st, a, g);
-    else hipLaunchKernelGGL((igemm_halo_kernel<f16_t, 0, false, false, 9, 0, 0, 0, true>), dim3(g.ntm * g.ntn), dim3(256), LDS_BYTES, st, a, g);
-    return (int)hipGetLastError();
+    return out6_run(halo_job(a, g, st), a.mx_chunks16 > 0);
 }
 int igemm_halo_out6_launch_multi(const void* halo_multi, unsigned blocks, hipStream_t st) {
-    const HaloMulti& m = *reinterpret_cast<const HaloMulti*>(halo_multi);
-    const int rc = out6_attrs();
-    if (rc != 0) return rc;
-    if (m.p[0].mx_chunks16 > 0) hipLaunchKernelGGL((igemm_halo_multi_kernel<f16_t, false, 9, 6, 0, 0, false, true>), dim3(blocks), dim3(256), LDS_BYTES, st, m);
-    else hipLaunchKernelGGL((igemm_halo_multi_kernel<f16_t, false, 9, 0, 0, 0, false, true>), dim3(blocks), dim3(256), LDS_BYTES, st, m);
-    return (int)hipGetLastError();
+    const HaloJob j = halo_job(halo_multi, blocks, st);
+    return out6_run(j, j.m->p[0].mx_chunks16 > 0);
 }
 }  // namespace omgsr

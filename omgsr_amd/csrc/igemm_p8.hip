@@ -24,6 +24,7 @@
 #include "common.hip.h"
 #include "../../include/omgsr_hip.h"
 #include "igemm_epilogue.hip.h"
+#include "igemm_launch.hip.h"
 #include <type_traits>
 
 namespace {
@@ -340,25 +341,9 @@ int igemm_p8_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st) {
     const int logical_cols = (a.act == OMGSR_ACT_GEGLU) ? 2 * a.Cout : a.Cout;
     g.ntm = (g.M + BM - 1) / BM;
     g.ntn = (logical_cols + BN - 1) / BN;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_p8_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_p8_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     dim3 grid(g.ntm * g.ntn, 1, a.batch);
-    if (a.mx_chunks16 > 0) {            // mixed-precision rows (fp16 compute type; the dispatcher checked igemm_gmx_ok)
-        static bool mx_attr = false;
-        if (!mx_attr) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(igemm_p8_kernel<f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            if (e != hipSuccess) return (int)e;
-            mx_attr = true;
-        }
-        hipLaunchKernelGGL((igemm_p8_kernel<f16_t, true>), grid, dim3(512), LDS_BYTES, st, a, g);
-        return (int)hipGetLastError();
-    }
-    OMGSR_DISPATCH_T(hipLaunchKernelGGL((igemm_p8_kernel<T>), grid, dim3(512), LDS_BYTES, st, a, g));
-    return (int)hipGetLastError();
+    // mixed-precision rows (fp16 compute type; the dispatcher checked igemm_gmx_ok)
+    if (a.mx_chunks16 > 0) return launch_lds<igemm_p8_kernel<f16_t, true>>(grid, dim3(512), LDS_BYTES, st, a, g);
+    OMGSR_DISPATCH_T(return launch_lds<igemm_p8_kernel<T>>(grid, dim3(512), LDS_BYTES, st, a, g));
 }
 }  // namespace omgsr

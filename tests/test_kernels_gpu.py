@@ -169,6 +169,10 @@ MULTI_CASES = [
     (256, 256, True, False, [(4, 43, 43), (4, 43, 32), (4, 32, 43), (4, 32, 32)]),           # upsampling conv: phase form, merged
     (128, 3, False, False, [(2, 96, 80), (2, 64, 80), (1, 64, 64)]),                         # conv_out: narrow shape
     (64, 128, False, False, [(1, 9, 33), (2, 16, 16)]),                                      # too small for the halo kernel even together
+    # the group kernels the cases above do not reach. Maps 46-80 wide: the FLAT form with the 27-piece patch, for the group (per image
+    # 10 / 8 flattened tiles against 12 spatial ones; 248 tiles >= the 192 the halo kernel wants) ...
+    (128, 128, False, True, [(20, 48, 48), (6, 48, 40)]),
+    (128, 3, False, False, [(4, 96, 80), (2, 64, 80)]),                                      # ... and conv_out with 144 + 48 = 192 tiles: the narrow group kernel
 ]
 
 

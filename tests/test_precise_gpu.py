@@ -301,15 +301,18 @@ def test_conv_mx_multi_launch_and_saturation():
     C, Cout = 128, 128
     w = torch.randn(Cout, C, 3, 3, generator=_g(9)) * (9 * C) ** -0.5
     pw = ops.pack_conv_weight(w, None, device=DEV, split=3)
-    xs = [torch.randn(n, h, wd, C, generator=_g(20 + i)) for i, (n, h, wd) in enumerate([(3, 40, 40), (1, 40, 32), (1, 32, 40), (1, 32, 32)])]
     ops.overflow_seen(); ops.mx_saturation_seen()                 # clear both bits of the guard word
-    ys = ops.conv2d_multi([x.to(DEV) for x in xs], pw, pad=1)
-    for x, y in zip(xs, ys):
-        ref = F.conv2d(x.permute(0, 3, 1, 2).double(), w.double(), padding=1).permute(0, 2, 3, 1)
-        assert _rel(y, ref) < 2e-5
+    # the tile-shape groups of a tiled-VAE level (FLAT plan for the whole group: 22-piece patch), a spatial group (one map too wide for the
+    # FLAT form), and a group of maps 46-80 wide (FLAT plan, 27-piece patch): the three group kernels of the format
+    for shapes in ([(3, 40, 40), (1, 40, 32), (1, 32, 40), (1, 32, 32)], [(2, 96, 96), (1, 96, 64), (1, 64, 96)], [(2, 48, 48), (1, 48, 40)]):
+        xs = [torch.randn(n, h, wd, C, generator=_g(20 + i)) for i, (n, h, wd) in enumerate(shapes)]
+        ys = ops.conv2d_multi([x.to(DEV) for x in xs], pw, pad=1)
+        for x, y in zip(xs, ys):
+            ref = F.conv2d(x.permute(0, 3, 1, 2).double(), w.double(), padding=1).permute(0, 2, 3, 1)
+            assert _rel(y, ref) < 2e-5
     torch.cuda.synchronize()
     assert not ops.mx_saturation_seen()
-    big = xs[0] * 3000.0                                          # |a| up to ~1e4: a_hi' clamps at 448, a_lo' 2^11 clamps too
+    big = torch.randn(3, 40, 40, C, generator=_g(20)) * 3000.0                                         # |a| up to ~1e4: a_hi' clamps at 448, a_lo' 2^11 clamps too
     y = ops.conv2d(big.to(DEV), pw, pad=1)
     ref = F.conv2d(big.permute(0, 3, 1, 2).double(), w.double(), padding=1).permute(0, 2, 3, 1)
     assert torch.isfinite(y).all() and _rel(y, ref) < 1e-3
@@ -1013,8 +1016,9 @@ def test_conv_mx6_multi_launch_split_k_and_refusals():
     C, Cout = 128, 128
     w = torch.randn(Cout, C, 3, 3, generator=_g(9)) * (9 * C) ** -0.5
     pw = ops.pack_conv_weight(w, None, device=DEV, split=4)
-    # the tile-shape groups of a tiled-VAE level in one launch (FLAT plan for the whole group), then a spatial group
-    for shapes in ([(3, 40, 40), (1, 40, 32), (1, 32, 40), (1, 32, 32)], [(2, 96, 96), (1, 96, 64), (1, 64, 96)]):
+    # the tile-shape groups of a tiled-VAE level in one launch (FLAT plan for the whole group), then a spatial group, then a group of maps
+    # 46-80 wide (FLAT plan with the 27-piece patch)
+    for shapes in ([(3, 40, 40), (1, 40, 32), (1, 32, 40), (1, 32, 32)], [(2, 96, 96), (1, 96, 64), (1, 64, 96)], [(2, 48, 48), (1, 48, 40)]):
         xs = [torch.randn(n, h, wd, C, generator=_g(20 + i)) for i, (n, h, wd) in enumerate(shapes)]
         ys = ops.conv2d_multi([ops.to_operand(x.to(DEV), 4) for x in xs], pw, pad=1)
         for x, y in zip(xs, ys):
