@@ -250,6 +250,32 @@ int omgsr_conv_mxfp8(const omgsr_igemm_args* a, void* stream);
  * mode; the entry points put it there themselves, whatever the field held). */
 int32_t omgsr_conv_mxfp8_multi_ok(const omgsr_igemm_args* args, int32_t count);
 int omgsr_conv_mxfp8_multi(const omgsr_igemm_args* args, int32_t count, void* stream);
+/* Additive under ABI v22 (no struct changed): the MXFP8 form of nearest-2x up-sampling + 3x3 stride-1 pad-1 convolution (mxfp8_conv_up_kernel: the
+ * fp8 tier's opt-in VAE up-samplers), as four 2 x 2 convolutions of the LOW-resolution map. The argument block of the same omgsr_igemm problem
+ * (upsample = 1, Ho = 2 H, Wo = 2 W) with
+ *   in        OMGSR_EL_MXFP8 codes  uint8 [N][H][W][Cin] of the low-resolution map (rows = pixels, K = Cin: what omgsr_quantize_mxfp8 writes)
+ *   in_scale  E8M0 [N][H][W][Cin / 32]
+ *   weight_ph codes uint8 [4 phases][Cin / 64][4 taps][Cout_pad][64]: the phase-summed 2 x 2 kernels (phase = 2 a + b of output pixel
+ *             (2 y + a, 2 x + b), tap = 2 dy + dx over input rows y - 1 + a + dy, columns x - 1 + b + dx), one MXFP8 block per 32 consecutive
+ *             input channels of one (phase, cout, tap), slice-major
+ *   w_scale   E8M0 [4 phases][Cin / 64][Cout_pad][2][4]: byte t = the scale of (phase, cout, tap t, block 2 chunk + b)
+ *   weight    unused (NULL or weight_ph); weight_cm unused; K_pad = 9 Cin; mxf8 = 0
+ * and every output option the 16-bit phase form has (bias, act, gate, bf16 / fp32 out, gn_partial as omgsr_igemm_gn_slots / _gn_entries answer
+ * for the same block: the four-phase slots). Pixels outside the map contribute exact zeros whatever the planes hold.
+ * omgsr_conv_mxfp8_up_ok: 1 when the problem is served (pointers may still be unset) - the geometry for which omgsr_igemm hands the bf16
+ * problem to the halo-tile kernel's phase form (its tile-count policy included; one sample's rows in batch-invariant mode), Cin % 128 == 0,
+ * Cin <= 512, Cout_pad % 128 == 0, bf16 compute type, none of the split / MX / mxf8 / GroupNorm-producer / out_lo_off / out_mx fields.
+ * omgsr_conv_mxfp8_up returns OMGSR_E_SHAPE for anything else (never another kernel).
+ * omgsr_conv_mxfp8_up_multi_ok / _multi: the problems of ONE tiled-VAE layer (the same weight_ph, w_scale, Cin, Cout, bias, act, gate, alpha and
+ * output kind; their own N / H / W and tensors) through mxfp8_conv_up_multi_kernel, at most 8 per launch (a larger `count` runs as successive
+ * launches of at most 8; a group of one launches mxfp8_conv_up_kernel). One answer per layer: every problem passes omgsr_conv_mxfp8_up_ok with
+ * the SUM of the problems' phase-form tile counts (4 N ceil(W / 32) ceil(H / 8) ceil(Cout / 128) each) in group_tiles - 0 in batch-invariant
+ * mode, where every problem is judged alone; the entry points put it there themselves. _multi returns OMGSR_E_SHAPE for anything _multi_ok
+ * refuses (never another kernel) and leaves each problem the GroupNorm partials its own omgsr_conv_mxfp8_up call would. */
+int32_t omgsr_conv_mxfp8_up_ok(const omgsr_igemm_args* a);
+int omgsr_conv_mxfp8_up(const omgsr_igemm_args* a, void* stream);
+int32_t omgsr_conv_mxfp8_up_multi_ok(const omgsr_igemm_args* args, int32_t count);
+int omgsr_conv_mxfp8_up_multi(const omgsr_igemm_args* args, int32_t count, void* stream);
 /* The problems of ONE layer that differ only in tensors and spatial extents (the tiled VAE runs every layer once per tile-shape group:
  * corner / edge / interior tiles are separate dense tensors; infer/vaehook.py:537-829 walks them one tile at a time). Call
  * omgsr_igemm_multi_plan first: it writes `group_tiles` into every problem, so that omgsr_igemm_gn_slots / _gn_entries /
@@ -571,7 +597,8 @@ int omgsr_timing_reset(void);
  * kernel's split-K (chunk ranges as one igemm_halo_multi_kernel launch + splitk_reduce_kernel), 13 / 14 / 15 the halo kernel with fp6
  * (OMGSR_EL_MX6) correction chunks: single, launch group, split-K, 16 / 17 the same in the phase-decomposed form: single, launch group,
  * 18 mxfp8_gemm_kernel (ABI v18), 21 mxfp8_conv_kernel (ABI v22), 22 mxfp8_conv_multi_kernel (several problems of one layer in one launch),
- * 24 mxfp8_gemm_multi_kernel (up to 4 independent MXFP8 GEMMs in one launch: omgsr_igemm_mxfp8_multi).
+ * 24 mxfp8_gemm_multi_kernel (up to 4 independent MXFP8 GEMMs in one launch: omgsr_igemm_mxfp8_multi), 25 mxfp8_conv_up_kernel (nearest-2x
+ * up-sampling + 3x3 conv in MXFP8, phase-decomposed), 26 mxfp8_conv_up_multi_kernel (several problems of one layer in one launch).
  * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19), 20 vae_attn_kernel (ABI v20, D = 512), 23 vae_attn_full_kernel (D = 512, every operand a two-term split). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;

@@ -744,6 +744,100 @@ extern "C" int omgsr_conv_mxfp8_multi(const omgsr_igemm_args* args, int32_t coun
     return 0;
 }
 
+// ---- additive under ABI v22: nearest-2x up-sampling + 3x3 conv in MXFP8 (conv_mxfp8_up.hip) ----------------------------------------------
+namespace {
+// Served: what mxfp8_conv_up_kernel runs AND the geometry for which this dispatcher hands the bf16 problem to the halo-tile kernel's phase
+// form (tile-count policy included, one sample's rows in batch-invariant mode): the fp8 form replaces that launch, nothing else
+bool conv_mxfp8_up_ok(omgsr_igemm_args a) {
+    if (a.in_ld == a.Cin) a.in_ld = 0;
+    if (!omgsr::mxfp8_conv_up_shape_ok(a)) return false;
+    if (!a.weight_ph) a.weight_ph = &a;             // (the answer does not depend on the pointers: the host asks before it packs)
+    a.workspace = nullptr;
+    return use_halo_phase(a);
+}
+
+// One answer for the layer: the group's total of phase-form tiles stands in every member's `group_tiles` (what omgsr_igemm_multi_plan writes
+// for a group of up-sampling problems); in batch-invariant mode it stays 0 and every member is judged alone from one sample's rows.
+int up_group_tiles(const omgsr_igemm_args* args, const int count) {
+    if (omgsr::g_batch_invariant) return 0;
+    int total = 0;
+    for (int i = 0; i < count; ++i) total += omgsr::igemm_halo_tiles(args[i], true);
+    return total;
+}
+
+bool conv_mxfp8_up_multi_ok(const omgsr_igemm_args* args, const int count) {
+    if (!args || count <= 0) return false;
+    const int total = up_group_tiles(args, count);
+    const omgsr_igemm_args& f = args[0];
+    for (int i = 0; i < count; ++i) {
+        omgsr_igemm_args a = args[i];
+        a.group_tiles = total;
+        if (!conv_mxfp8_up_ok(a)) return false;
+        const bool same = a.weight_ph == f.weight_ph && a.w_scale == f.w_scale && a.Cin == f.Cin && a.Cout == f.Cout && a.Cout_pad == f.Cout_pad &&
+                          a.K_pad == f.K_pad && a.bias == f.bias && a.gate == f.gate && a.alpha == f.alpha && a.act == f.act && a.out_dtype == f.out_dtype &&
+                          a.out_ld == f.out_ld && (a.gn_partial != nullptr) == (f.gn_partial != nullptr) && a.gn_groups == f.gn_groups &&
+                          a.gn_entries == f.gn_entries && a.overflow_flag == f.overflow_flag;
+        if (!same) return false;
+    }
+    return true;
+}
+
+// an argument block as the launch sees it
+int conv_mxfp8_up_member(const omgsr_igemm_args& in, const int group_tiles, omgsr_igemm_args& a) {
+    a = in;
+    if (!a.in_scale || !a.w_scale || !a.weight_ph) return OMGSR_E_BADARG;
+    if (!a.weight) a.weight = a.weight_ph;          // (the row-major packing does not exist in this form)
+    a.group_tiles = group_tiles;
+    a.workspace = nullptr;
+    return validate_args(a);
+}
+}  // namespace
+
+extern "C" int32_t omgsr_conv_mxfp8_up_ok(const omgsr_igemm_args* ap) { return (ap && conv_mxfp8_up_ok(*ap)) ? 1 : 0; }
+
+extern "C" int omgsr_conv_mxfp8_up(const omgsr_igemm_args* ap, void* stream) {
+    if (!ap) return OMGSR_E_BADARG;
+    omgsr_igemm_args a;
+    {
+        const int rc = conv_mxfp8_up_member(*ap, ap->group_tiles, a);
+        if (rc != 0) return rc;
+    }
+    if (!conv_mxfp8_up_ok(a)) return OMGSR_E_SHAPE;
+    double flops, bytes;
+    work_of(a, &flops, &bytes);
+    return omgsr::mxfp8_conv_up_launch(a, geo_of(a), (hipStream_t)stream, flops);
+}
+
+extern "C" int32_t omgsr_conv_mxfp8_up_multi_ok(const omgsr_igemm_args* args, int32_t count) { return conv_mxfp8_up_multi_ok(args, count) ? 1 : 0; }
+
+extern "C" int omgsr_conv_mxfp8_up_multi(const omgsr_igemm_args* args, int32_t count, void* stream) {
+    if (!args || count <= 0) return OMGSR_E_BADARG;
+    if (!conv_mxfp8_up_multi_ok(args, count)) return OMGSR_E_SHAPE;
+    const int total = up_group_tiles(args, count);
+    for (int i = 0; i < count; ++i) {                   // every member is checked before the first launch
+        omgsr_igemm_args a;
+        const int rc = conv_mxfp8_up_member(args[i], total, a);
+        if (rc != 0) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int at = 0; at < count; at += MXC_MULTI_MAX) {
+        const int ng = count - at < MXC_MULTI_MAX ? count - at : MXC_MULTI_MAX;
+        omgsr_igemm_args grp[MXC_MULTI_MAX];
+        Geo geo[MXC_MULTI_MAX];
+        double gf = 0.0;
+        for (int i = 0; i < ng; ++i) {
+            conv_mxfp8_up_member(args[at + i], total, grp[i]);
+            double f, b;
+            work_of(grp[i], &f, &b);
+            gf += f;
+            geo[i] = geo_of(grp[i]);
+        }
+        const int rc = ng == 1 ? omgsr::mxfp8_conv_up_launch(grp[0], geo[0], st, gf) : omgsr::mxfp8_conv_up_launch_multi(grp, geo, ng, st, gf);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
 // Additive under ABI v22: an mxf8 problem whose output is written in the OMGSR_EL_MXFP8 form (include/omgsr_hip.h) - mxfp8_gemm_kernel's OUT8
 // instantiation or nothing. The scale plane travels next to the argument block, whose layout does not change.
 extern "C" int omgsr_igemm_out_mxfp8(const omgsr_igemm_args* ap, void* out_scale, int64_t out_scale_ld, void* stream) {

@@ -153,6 +153,23 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
         self._pk8, self._pk8_key = None, None
         bump_cache_epoch()
 
+    # the fp8 tier (precision.set_fp8_upsample): an up-sampling conv (Upsample2D) whose problems the library serves (ops.conv2d fp8_up_pack) run
+    # as mxfp8_conv_up_kernel behind one quantize pass over the low-resolution map; packed lazily like the nine-tap MXFP8 form, under its own key
+    fp8_up = False
+
+    def packed_mxfp8_up(self) -> ops.PackedWeight:
+        k = _key(self.weight, self.bias, "mxfp8-conv-up")
+        if getattr(self, "_pk8u_key", None) != k:
+            bump_cache_epoch()
+            _log_rebuild(self._drop_packed_mxfp8_up)
+            self._pk8u = ops.pack_conv_weight_mxfp8_up(self.weight, self.bias)
+            self._pk8u_key = k
+        return self._pk8u
+
+    def _drop_packed_mxfp8_up(self) -> None:
+        self._pk8u, self._pk8u_key = None, None
+        bump_cache_epoch()
+
     def packed(self) -> ops.PackedWeight:
         # logical Cout widened to a multiple of 8 (zero rows): 3/4-channel heads write 16-byte NHWC rows
         sp, wsp, ph = self.in_split(), self.in_wsplit(), self.phase_upsample
@@ -171,8 +188,9 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
         if out_dtype == ops.OUT_STREAM and self.out_inner16 and ops.precise():
             out_dtype = ops.OUT_BF16
         fp8_pack = self.packed_mxfp8 if (self.fp8 and gn is not None and bias_override is None) else None
+        fp8_up_pack = self.packed_mxfp8_up if (self.fp8_up and upsample and gn is None and bias_override is None) else None
         return ops.conv2d(x, pw, stride=stride or self.stride[0], pad=p, upsample=upsample, act=act, residual=residual,
-                          gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack)
+                          gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack, fp8_up_pack=fp8_up_pack)
 
     def nhwc_multi(self, xs, *, pad=None, upsample=False, act=ops.ACT_NONE, residuals=None, stride=None, gn_groups=0,
                    out_dtype=ops.OUT_STREAM, out_split=1, gn=None, fp8=False):
@@ -183,8 +201,9 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
         if out_dtype == ops.OUT_STREAM and self.out_inner16 and ops.precise():
             out_dtype = ops.OUT_BF16
         fp8_pack = self.packed_mxfp8 if (fp8 and self.fp8 and gn is not None) else None
+        fp8_up_pack = self.packed_mxfp8_up if (fp8 and self.fp8_up and upsample and gn is None) else None
         return ops.conv2d_multi(list(xs), pw, stride=stride or self.stride[0], pad=p, upsample=upsample, act=act, residuals=residuals,
-                                gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack)
+                                gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack, fp8_up_pack=fp8_up_pack)
 
     def forward(self, x):  # NCHW compat
         y = self.nhwc(ops.nchw_to_nhwc(x.contiguous(), ops._round_up(self.in_channels, 8)))

@@ -703,6 +703,33 @@ def pack_conv_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor], d
     return PackedWeight(codes.view(cin // 64 * 9 * cout_pad, 64), b, cout8, cin, 3, 3, w_cm=codes, w_scale=sc)
 
 
+def pack_conv_weight_mxfp8_up(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> PackedWeight:
+    """[Cout, Cin, 3, 3] bf16 -> the weight of omgsr_conv_mxfp8_up (include/omgsr_hip.h): the four phase-summed 2 x 2 kernels of a 3x3 conv
+    applied to a nearest-2x up-sampled map (_phase_kernels: fp64 sums, phase 2a + b, tap 2 dy + dx), one MXFP8 block per 32 consecutive input
+    channels of one (phase, cout, tap), quantised on the device by quantize_mxfp8 (rows = (phase, cout, tap), K = Cin, from the fp32 sums), then
+    laid out slice-major: `w_ph` codes uint8 [4][Cin/64][4][Cout_pad][64], `w_scale` uint8 [4][Cin/64][Cout_pad][2][4] (byte t = tap t of that
+    (phase, chunk, cout, block)). Rows are padded with zeros to a multiple of 128; `w` is the codes tensor too."""
+    if _PRECISE or _ACT != torch.bfloat16:
+        raise ValueError("an fp8 (MXFP8) layer needs the bf16 compute type (the fp8 tier); the accurate tier and fp16 have none")
+    dev = device or weight.device
+    cout, cin, R, S = weight.shape
+    if (R, S) != (3, 3) or cin % 128:
+        raise ValueError(f"an fp8 (MXFP8) up-sampling conv needs a 3x3 kernel and in_channels % 128 == 0, got {tuple(weight.shape)}")
+    cout8 = _round_up(cout, 8)
+    cout_pad = _round_up(cout8, 128)
+    ph = _phase_kernels(weight.detach().to(device=dev, dtype=torch.bfloat16).permute(0, 2, 3, 1).float())      # [4, Cout, 2, 2, Cin]
+    w = torch.zeros((4, cout_pad, 4, cin), device=dev, dtype=torch.float32)
+    w[:, :cout] = ph.reshape(4, cout, 4, cin)
+    q = quantize_mxfp8(w)
+    codes = q.codes.view(4, cout_pad, 4, cin // 64, 64).permute(0, 3, 2, 1, 4).contiguous()           # [phase][chunk][tap][cout][64]
+    sc = q.scales.view(4, cout_pad, 4, cin // 64, 2).permute(0, 3, 1, 4, 2).contiguous()                # [phase][chunk][cout][block][tap]
+    b = None
+    if bias is not None:
+        b = torch.zeros(cout8, device=dev, dtype=torch.float32)
+        b[:cout] = bias.detach().to(device=dev, dtype=torch.float32)
+    return PackedWeight(codes.view(-1, 64), b, cout8, cin, 3, 3, w_ph=codes, w_scale=sc)
+
+
 # --------------------------------------------------------------------------------------------
 # K1-K3, K5, K6: implicit-GEMM conv / linear / bmm
 
@@ -939,7 +966,7 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: tuple[int
            upsample: bool = False, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
            gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM, alpha: float = 1.0,
            out: Optional[torch.Tensor] = None, gn_groups: int = 0, out_split: int = 1, sample_rows: int = 0,
-           gn: Optional["GnSpec"] = None, fp8_pack=None) -> torch.Tensor:
+           gn: Optional["GnSpec"] = None, fp8_pack=None, fp8_up_pack=None) -> torch.Tensor:
     """x [N,H,W,Cin] operand (or a stream tensor: cast / split here) -> [N,Ho,Wo,Cout]. pad = (top, bottom, left, right) on
     the (virtual) input. out_dtype: OUT_STREAM (a stream tensor: default), OUT_BF16 (a 16-bit operand for the next GEMM,
     `out_split` 2 = written as the two-term split) or OUT_F32. residual: a stream tensor of the output's shape.
@@ -949,13 +976,19 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: tuple[int
     patch producer where the library can, the apply pass in front of the conv otherwise.
     fp8_pack (a layer marked by precision.set_fp8_conv; needs gn): a callable returning the layer's pack_conv_weight_mxfp8 form. Where
     omgsr_conv_mxfp8_ok accepts the problem (a per-problem decision from one sample's geometry), the GroupNorm runs as the apply pass that
-    writes MXFP8 and mxfp8_conv_kernel runs the conv; otherwise the call takes the 16-bit path below exactly as without it."""
+    writes MXFP8 and mxfp8_conv_kernel runs the conv; otherwise the call takes the 16-bit path below exactly as without it.
+    fp8_up_pack (upsample=True on a layer marked by precision.set_fp8_upsample; no gn, no residual): a callable returning the layer's
+    pack_conv_weight_mxfp8_up form. Where omgsr_conv_mxfp8_up_ok accepts the problem, x goes through quantize_mxfp8 (one pass over the
+    low-resolution map) and mxfp8_conv_up_kernel runs the conv; otherwise the call takes the 16-bit path below exactly as without it."""
     a = IgemmArgs()
     if gn is not None and not _gn_candidate(x, pw):
         x, gn = gn.apply(x, pw.split), None
     x, out = _conv_args(a, x, pw, stride, pad, upsample, act, residual, gate, out_dtype, alpha, out, out_split, sample_rows)
     if fp8_pack is not None and gn is not None and out_split == 1 and _lib.load().omgsr_conv_mxfp8_ok(C.byref(a)):
         return _conv2d_mxfp8(a, gn.apply(x, 5), fp8_pack(), out, gn_groups)
+    if (fp8_up_pack is not None and upsample and gn is None and residual is None and out_split == 1
+            and _lib.load().omgsr_conv_mxfp8_up_ok(C.byref(a))):
+        return _conv2d_mxfp8_up(a, quantize_mxfp8(x), fp8_up_pack(), out, gn_groups)
     if out_split == 4 and not _lib.load().omgsr_igemm_out_mx6_ok(C.byref(a)):
         # the fp6 operand form comes out of the halo-tile kernel's dedicated instantiations only: anything else writes a stream tensor and the
         # cast kernel makes the operand (one more pass over the tensor; small maps and GEMM-shaped problems)
@@ -1067,19 +1100,98 @@ def conv2d_mxfp8_multi(xqs, pw8: PackedWeight, *, act: int = ACT_NONE, residuals
     return _conv2d_mxfp8_multi(arr, n, xqs, pw8, outs, gn_groups)
 
 
+def _fill_conv_mxfp8_up(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight) -> None:
+    """Operand and weight side of an argument block filled for the 16-bit form of the same up-sampling problem -> the MXFP8 form's."""
+    if pw8.w_ph is None or not pw8.fp8 or xq.codes.shape[-1] != pw8.cin or a.Cout != pw8.cout:
+        raise ValueError(f"conv2d_mxfp8_up: operand K {xq.codes.shape[-1]} / Cout {a.Cout} do not match a pack_conv_weight_mxfp8_up weight "
+                         f"({pw8.cin}, {pw8.cout})")
+    a.in_, a.in_scale = xq.codes.data_ptr(), xq.scales.data_ptr()
+    a.weight, a.weight_ph, a.w_scale, a.weight_cm = pw8.w_ph.data_ptr(), pw8.w_ph.data_ptr(), pw8.w_scale.data_ptr(), None
+    a.Cout_pad, a.K_pad = pw8.w_ph.shape[3], 9 * pw8.cin
+    a.bias = _ptr(pw8.bias) if a.bias is None else a.bias
+
+
+def _conv2d_mxfp8_up(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight, out: torch.Tensor, gn_groups: int) -> torch.Tensor:
+    """Launch omgsr_conv_mxfp8_up on an argument block filled for the 16-bit form of the same problem (geometry, epilogue, output)."""
+    _fill_conv_mxfp8_up(a, xq, pw8)
+    a.workspace, a.group_tiles = None, 0
+    partial = _conv_gn(a, gn_groups, 1, out.device)
+    check(_lib.load().omgsr_conv_mxfp8_up(C.byref(a), _stream()), "omgsr_conv_mxfp8_up")
+    if partial is not None:
+        _leave_gn(out, partial, gn_groups)
+    return out
+
+
+def _conv_mxfp8_up_args(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight, act: int, out_dtype: int, sample_rows: int) -> torch.Tensor:
+    """Geometry, epilogue and output of one nearest-2x + 3x3 stride-1 pad-1 MXFP8 conv problem; returns the output it allocated."""
+    N, H, W, Cin = xq.codes.shape
+    out = _out_tensor((N, 2 * H, 2 * W), pw8.cout, out_dtype, 1, xq.codes.device)
+    _fill_out(a, out, 1, None, pw8.cout)
+    a.N, a.H, a.W, a.Ho, a.Wo, a.Cin, a.Cout = N, H, W, 2 * H, 2 * W, Cin, pw8.cout
+    a.R, a.S, a.stride, a.pad_top, a.pad_left, a.upsample = 3, 3, 1, 1, 1, 1
+    a.act, a.batch, a.alpha, a.sample_rows = act, 1, 1.0, sample_rows or 4 * H * W
+    a.overflow_flag = _ovf(xq.codes.device)
+    return out
+
+
+def conv2d_mxfp8_up(xq: "Mxfp8", pw8: PackedWeight, *, act: int = ACT_NONE, gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM,
+                    gn_groups: int = 0, sample_rows: int = 0) -> torch.Tensor:
+    """conv3x3(nearest_up2(x)), stride 1, pad 1, of an MXFP8 operand xq [N,H,W,Cin] (quantize_mxfp8 of the low-resolution map) with a
+    pack_conv_weight_mxfp8_up weight -> [N,2H,2W,Cout8]. No other kernel stands behind it: a problem omgsr_conv_mxfp8_up_ok does not accept
+    raises (OMGSR_E_SHAPE)."""
+    if not isinstance(xq, Mxfp8) or not pw8.fp8 or pw8.w_ph is None:
+        raise ValueError("conv2d_mxfp8_up: an Mxfp8 operand and a pack_conv_weight_mxfp8_up weight")
+    a = IgemmArgs()
+    out = _conv_mxfp8_up_args(a, xq, pw8, act, out_dtype, sample_rows)
+    a.gate = _ptr(gate)
+    return _conv2d_mxfp8_up(a, xq, pw8, out, gn_groups)
+
+
+def _conv2d_mxfp8_up_multi(arr, n: int, xqs, pw8: PackedWeight, outs, gn_groups: int):
+    """Launch omgsr_conv_mxfp8_up_multi on argument blocks filled for the 16-bit form of the same problems (omgsr_conv_mxfp8_up_multi_ok said 1)."""
+    # the group's total of phase-form workgroup tiles: what `group_tiles` holds when the library plans a member's GroupNorm partials
+    total = 0 if _BATCH_INVARIANT else sum(4 * arr[i].N * ((arr[i].W + 31) // 32) * ((arr[i].H + 7) // 8) * ((arr[i].Cout + 127) // 128) for i in range(n))
+    partials = []
+    for i in range(n):
+        _fill_conv_mxfp8_up(arr[i], xqs[i], pw8)
+        arr[i].workspace, arr[i].group_tiles = None, total
+        partials.append(_conv_gn(arr[i], gn_groups, 1, outs[i].device))
+    check(_lib.load().omgsr_conv_mxfp8_up_multi(arr, n, _stream()), "omgsr_conv_mxfp8_up_multi")
+    for out, partial in zip(outs, partials):
+        if partial is not None:
+            _leave_gn(out, partial, gn_groups)
+    return outs
+
+
+def conv2d_mxfp8_up_multi(xqs, pw8: PackedWeight, *, act: int = ACT_NONE, out_dtype: int = OUT_STREAM, gn_groups: int = 0):
+    """conv2d_mxfp8_up of several MXFP8 operands xqs[k] [N_k, H_k, W_k, Cin] with ONE pack_conv_weight_mxfp8_up weight (the tile-shape groups of
+    a tiled-VAE layer) through omgsr_conv_mxfp8_up_multi: one launch of mxfp8_conv_up_multi_kernel per 8 problems, served as a GROUP. No other
+    kernel stands behind it: a group omgsr_conv_mxfp8_up_multi_ok does not accept raises (OMGSR_E_SHAPE). Same bytes as one conv2d_mxfp8_up call
+    per operand where those are served. Returns the list of outputs."""
+    xqs = list(xqs)
+    if not xqs or not all(isinstance(xq, Mxfp8) for xq in xqs) or not pw8.fp8 or pw8.w_ph is None:
+        raise ValueError("conv2d_mxfp8_up_multi: Mxfp8 operands and a pack_conv_weight_mxfp8_up weight")
+    n = len(xqs)
+    arr = (IgemmArgs * n)()
+    outs = [_conv_mxfp8_up_args(arr[i], xq, pw8, act, out_dtype, 0) for i, xq in enumerate(xqs)]
+    return _conv2d_mxfp8_up_multi(arr, n, xqs, pw8, outs, gn_groups)
+
+
 def conv2d_multi(xs, pw: PackedWeight, *, stride: int = 1, pad: tuple[int, int, int, int] | int = 1, upsample: bool = False,
                  act: int = ACT_NONE, residuals=None, out_dtype: int = OUT_STREAM, gn_groups: int = 0, out_split: int = 1,
-                 gn: Optional["GnSpec"] = None, fp8_pack=None):
+                 gn: Optional["GnSpec"] = None, fp8_pack=None, fp8_up_pack=None):
     """conv2d of several inputs with ONE weight (the tile-shape groups of a tiled-VAE layer: each x is its own dense [T*N, h, w, C]
     tensor) through omgsr_igemm_multi: the problems that take the halo-tile kernel run as one launch, with the kernel choice and the
     fused GroupNorm statistics planned for the group. Same results as a conv2d call per input. Returns the list of outputs.
     fp8_pack (see conv2d; needs gn and out_split 1): where omgsr_conv_mxfp8_multi_ok accepts the GROUP, the layer is one apply-to-MXFP8
     launch (group_norm_apply_mxfp8_multi) and one mxfp8_conv_multi_kernel launch; otherwise the WHOLE layer takes the 16-bit path below
-    exactly as without it - one form per layer, tiles of one image never see different arithmetic."""
+    exactly as without it - one form per layer, tiles of one image never see different arithmetic.
+    fp8_up_pack (see conv2d; upsample=True, no gn, no residuals): where omgsr_conv_mxfp8_up_multi_ok accepts the GROUP, the layer is one
+    quantize_mxfp8 pass per tile-shape group and one mxfp8_conv_up_multi_kernel launch; otherwise the WHOLE layer takes the 16-bit path."""
     n = len(xs)
     if n == 1:
         return [conv2d(xs[0], pw, stride=stride, pad=pad, upsample=upsample, act=act, residual=None if residuals is None else residuals[0],
-                       out_dtype=out_dtype, gn_groups=gn_groups, out_split=out_split, gn=gn, fp8_pack=fp8_pack)]
+                       out_dtype=out_dtype, gn_groups=gn_groups, out_split=out_split, gn=gn, fp8_pack=fp8_pack, fp8_up_pack=fp8_up_pack)]
     lib = _lib.load()
     if gn is not None and not all(_gn_candidate(x, pw) for x in xs):
         xs, gn = [gn.apply(x, pw.split) for x in xs], None
@@ -1097,6 +1209,9 @@ def conv2d_multi(xs, pw: PackedWeight, *, stride: int = 1, pad: tuple[int, int, 
         for k in range(0, n, _lib.GN_MAX_GROUPS):
             xqs += group_norm_apply_mxfp8_multi(keep[k:k + _lib.GN_MAX_GROUPS], gn.mean, gn.rstd, gn.gamma, gn.beta, gn.groups, gn.act)
         return _conv2d_mxfp8_multi(arr, n, xqs, fp8_pack(), outs, gn_groups)
+    if (fp8_up_pack is not None and upsample and gn is None and residuals is None and out_split == 1
+            and lib.omgsr_conv_mxfp8_up_multi_ok(arr, n)):
+        return _conv2d_mxfp8_up_multi(arr, n, [quantize_mxfp8(x) for x in keep], fp8_up_pack(), outs, gn_groups)
     check(lib.omgsr_igemm_multi_plan(arr, n), "omgsr_igemm_multi_plan")
     if out_split == 4 and not all(lib.omgsr_igemm_out_mx6_ok(C.byref(arr[i])) for i in range(n)):
         ys = conv2d_multi(keep, pw, stride=stride, pad=pad, upsample=upsample, act=act, residuals=residuals, out_dtype=OUT_STREAM, gn=gn)

@@ -48,21 +48,24 @@ class OMGSR_F_Infer(torch.nn.Module):
         # precision_policy={"flux": {"fp8": [patterns]}} narrows the list). Modules are held and LoRA-merged in bf16, their fp8 forms packed lazily.
         # precision_policy={"flux": {"fp8_attention": True | [block patterns]}} (fp8 tier only, opt-in) also runs those blocks' joint attention
         # on MXFP8 q / k / V^T (precision.set_fp8_attention). precision_policy={"vae": {"fp8": True | [layer patterns]}} (fp8 tier only, opt-in)
-        # runs those resnet convs of the VAE as MXFP8 convolutions where the kernel serves them (precision.set_fp8_conv); the tiled VAE serves them with
+        # runs those resnet convs of the VAE as MXFP8 convolutions where the kernel serves them (precision.set_fp8_conv), {"vae": {"fp8_upsample":
+        # True | [layer patterns]}} the decoder's up-sampling convs (precision.set_fp8_upsample); the tiled VAE serves either with
         # _init_tiled_vae(fp8_convs=True) only.
         fp8 = weight_dtype == torch.float8_e4m3fn
         if fp8 and precision_policy is not None and not (isinstance(precision_policy, dict) and set(precision_policy) <= {"flux", "vae"} and
                                                          isinstance(precision_policy.get("flux", {}), dict) and
                                                          isinstance(precision_policy.get("vae", {}), dict) and
                                                          set(precision_policy.get("flux", {})) <= {"fp8", "fp8_attention"} and
-                                                         set(precision_policy.get("vae", {})) <= {"fp8"}):
+                                                         set(precision_policy.get("vae", {})) <= {"fp8", "fp8_upsample"}):
             raise ValueError("the fp8 tier's precision_policy is {'flux': {'fp8': [patterns], 'fp8_attention': True | [block patterns]}, "
-                             "'vae': {'fp8': True | [layer patterns]}}")
+                             "'vae': {'fp8': True | [layer patterns], 'fp8_upsample': True | [layer patterns]}}")
         if not fp8:
-            from ..precision import refuse_fp8_attention, refuse_fp8_conv
+            from ..precision import refuse_fp8_attention, refuse_fp8_conv, refuse_fp8_upsample
             refuse_fp8_attention(precision_policy, f"the {weight_dtype} tier")
             refuse_fp8_conv(precision_policy, f"the {weight_dtype} tier")
+            refuse_fp8_upsample(precision_policy, f"the {weight_dtype} tier")
         fp8_vae = (precision_policy or {}).get("vae", {}).get("fp8") if fp8 else None
+        fp8_up = (precision_policy or {}).get("vae", {}).get("fp8_upsample") if fp8 else None
         fp8_patterns = (precision_policy or {}).get("flux", {}).get("fp8") if fp8 else None
         fp8_attention = (precision_policy or {}).get("flux", {}).get("fp8_attention") if fp8 else None
         weight_dtype = torch.bfloat16 if fp8 else weight_dtype
@@ -106,6 +109,13 @@ class OMGSR_F_Infer(torch.nn.Module):
         else:
             clear_fp8_conv(self.vae)
         self.fp8_vae = bool(fp8 and fp8_vae not in (None, False))
+        # {"vae": {"fp8_upsample": ...}} (opt-in, with or without "fp8"): the decoder's up-sampling convs as MXFP8 phase convolutions
+        from ..precision import clear_fp8_upsample, set_fp8_upsample
+        if fp8 and fp8_up not in (None, False):
+            set_fp8_upsample(self.vae, fp8_up)
+        else:
+            clear_fp8_upsample(self.vae)
+        self.fp8_vae_upsample = bool(fp8 and fp8_up not in (None, False))
         if weight_dtype == torch.float32:
             from ..precision import resolve
             resolve(precision_policy, vae=self.vae, flux=self.flux_transformer)
@@ -147,15 +157,15 @@ class OMGSR_F_Infer(torch.nn.Module):
 
     def _init_tiled_vae(self, encoder_tile_size=256, decoder_tile_size=256, fast_decoder=False, fast_encoder=False,
                         color_fix=False, vae_to_gpu=True, fp8_convs=False):
-        """fp8_convs=True (needs precision_policy {'vae': {'fp8': ...}}): the hooks serve the marked convs with the MXFP8 kernels, one form per
-        layer (VAEHook.fp8_convs). Without it the key and the tiled VAE stay exclusive."""
-        fp8_vae = getattr(self, "fp8_vae", False)
+        """fp8_convs=True (needs precision_policy {'vae': {'fp8': ...}} and / or {'vae': {'fp8_upsample': ...}}): the hooks serve the marked
+        convs with the MXFP8 kernels, one form per layer (VAEHook.fp8_convs). Without it the keys and the tiled VAE stay exclusive."""
+        fp8_vae = getattr(self, "fp8_vae", False) or getattr(self, "fp8_vae_upsample", False)      # either key marks layers the hooks must be told to serve
         if fp8_vae and not fp8_convs:
-            raise ValueError("the tiled VAE is not served by the fp8 VAE convolutions (precision_policy {'vae': {'fp8': ...}}) unless asked: its "
+            raise ValueError("the tiled VAE is not served by the fp8 VAE convolutions (precision_policy {'vae': {'fp8' | 'fp8_upsample': ...}}) unless asked: its "
                              "launch groups run the bf16 kernels - pass fp8_convs=True to serve them in MXFP8, or build the pipeline without "
                              "that key to tile")
         if fp8_convs and not fp8_vae:
-            raise ValueError("fp8_convs=True needs the fp8 tier with precision_policy {'vae': {'fp8': True | [layer patterns]}}: no VAE conv is marked")
+            raise ValueError("fp8_convs=True needs the fp8 tier with precision_policy {'vae': {'fp8' | 'fp8_upsample': True | [layer patterns]}}: no VAE conv is marked")
         from .vaehook import VAEHook
         self.vae.encoder._tile_hook = VAEHook(self.vae.encoder, encoder_tile_size, is_decoder=False, fast_decoder=fast_decoder,
                                               fast_encoder=fast_encoder, color_fix=color_fix, to_gpu=vae_to_gpu)

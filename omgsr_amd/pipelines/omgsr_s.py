@@ -34,8 +34,9 @@ class OMGSR_S_Infer(torch.nn.Module):
             raise ValueError("OMGSR-S has no fp8 tier (the fp8 tier is OMGSR-F's DiT token GEMMs): use bfloat16, float16 or float32")
         from ..precision import refuse_fp8_attention
         refuse_fp8_attention(precision_policy, "OMGSR-S")
-        from ..precision import refuse_fp8_conv
+        from ..precision import refuse_fp8_conv, refuse_fp8_upsample
         refuse_fp8_conv(precision_policy, "OMGSR-S")
+        refuse_fp8_upsample(precision_policy, "OMGSR-S")
         # --weight_dtype picks the tier: bf16 / fp16 = that 16-bit type end to end; fp32 = the accurate tier (fp32 stream
         # tensors, fp16 MFMA operands, two-term split operands where the precision policy says so)
         ops.set_compute_dtype(weight_dtype)

@@ -316,7 +316,8 @@ def fp8_layers(model: nn.Module) -> list:
 # MXFP8 x MXFP8 convolution (mxfp8_conv_kernel) behind a GroupNorm + SiLU apply pass that writes MXFP8, wherever the library serves the problem
 # (omgsr_conv_mxfp8_ok: the halo-tile kernel's spatial form, Cin % 128 == 0); every other problem of a marked layer takes the bf16 path as
 # before. VAE_FP8_ELIGIBLE is the hard limit - the resnet conv1 / conv2 of encoder, decoder and both mid blocks, the only convs that read a
-# GroupNorm + SiLU output; conv_in / conv_out, the quant convs, the samplers and conv_shortcut never move. VAE_FP8 is what `True` marks: the
+# GroupNorm + SiLU output; conv_in / conv_out, the quant convs, the samplers and conv_shortcut never move under this key (the decoder's
+# up-samplers have a key of their own: VAE_FP8_UP_ELIGIBLE below). VAE_FP8 is what `True` marks: the
 # DECODER's 28 layers. Every eligible shape is faster in MXFP8 (1.19-1.70x, profiles/fp8_vae.json), but with all 48 layers the full-depth
 # OMGSR-F 256 -> 1024 output falls to 29.0-30.0 dB against the accurate tier (target >= 30 dB on three draws; the fp8 tier alone: 32.8-34.4);
 # decoder only holds 30.4-31.5 dB, encoder only 30.7-31.9 (DESIGN.md 3.4 has the per-group table). Encoder layers still move when named.
@@ -376,6 +377,65 @@ def refuse_fp8_conv(policy, where: str) -> None:
     """ValueError when a precision_policy asks for fp8 VAE convolutions outside the fp8 tier."""
     if isinstance(policy, dict) and isinstance(policy.get("vae"), dict) and "fp8" in policy["vae"]:
         raise ValueError(f"vae fp8 belongs to OMGSR-F's fp8 tier (weight_dtype=torch.float8_e4m3fn), not to {where}")
+
+
+# The VAE decoder's up-sampling convolutions in the fp8 tier (opt-in: precision_policy={"vae": {"fp8_upsample": True | [patterns]}}, with or
+# without the "fp8" key): a marked Upsample2D conv runs as mxfp8_conv_up_kernel - the phase-decomposed form on MXFP8 codes - behind one
+# quantize_mxfp8 pass over the low-resolution stream tensor, wherever the library serves the problem (omgsr_conv_mxfp8_up_ok: the halo-tile
+# kernel's phase form, Cin % 128 == 0, Cin <= 512); every other problem of a marked layer takes the bf16 path as before.
+# VAE_FP8_UP_ELIGIBLE is the hard limit and what `True` marks; VAE_FP8 / VAE_FP8_ELIGIBLE and what {"fp8": True} marks do not change.
+VAE_FP8_UP_ELIGIBLE = [r"^decoder\.up_blocks\.\d+\.upsamplers\.0\.conv$"]
+
+
+def _fp8_upsample_candidates(model: nn.Module):
+    elig = [re.compile(p) for p in VAE_FP8_UP_ELIGIBLE]
+    return [(name, m) for name, m in model.named_modules() if isinstance(m, Conv2d) and any(r.search(name) for r in elig)]
+
+
+def set_fp8_upsample(model: nn.Module, patterns) -> int:
+    """Mark the up-sampling convs of an AutoencoderKL whose names match `patterns` (a list of regular expressions, re.search; True = every
+    layer of VAE_FP8_UP_ELIGIBLE) as fp8 (nn.Conv2d.fp8_up); every other conv is unmarked. ValueError for anything else than True or a list
+    of strings, for a pattern that names no eligible layer, and outside the bf16 compute type. Returns how many layers are marked."""
+    from . import ops
+    if ops.precise() or ops.act_dtype() != torch.bfloat16:
+        raise ValueError("fp8 up-sampling convolutions need the bf16 compute type (the fp8 tier); the accurate tier and fp16 have none")
+    if patterns is True:
+        patterns = list(VAE_FP8_UP_ELIGIBLE)
+    elif not isinstance(patterns, (list, tuple)) or not patterns or not all(isinstance(p, str) for p in patterns):
+        raise ValueError(f"vae fp8_upsample is True or a list of layer-name patterns, got {patterns!r}")
+    regs = [re.compile(p) for p in patterns]
+    cand = _fp8_upsample_candidates(model)
+    dead = [r.pattern for r in regs if not any(r.search(name) for name, _ in cand)]
+    if dead:            # a typo would otherwise run the 16-bit up-samplers without a word
+        raise ValueError(f"vae fp8_upsample patterns that name no eligible layer (the decoder's up_blocks.N.upsamplers.0.conv): {dead}")
+    _touch()
+    want = {name for name, _ in cand if any(r.search(name) for r in regs)}
+    n = 0
+    for name, m in model.named_modules():
+        if isinstance(m, Conv2d):
+            m.fp8_up = name in want
+            n += m.fp8_up
+    return n
+
+
+def clear_fp8_upsample(model: nn.Module) -> None:
+    """Unmark every fp8 up-sampling conv of `model`."""
+    if any(isinstance(m, Conv2d) and m.fp8_up for m in model.modules()):
+        _touch()
+        for m in model.modules():
+            if isinstance(m, Conv2d):
+                m.fp8_up = False
+
+
+def fp8_upsample_layers(model: nn.Module) -> list:
+    """Names of the fp8 up-sampling convs of `model`."""
+    return [name for name, m in model.named_modules() if isinstance(m, Conv2d) and m.fp8_up]
+
+
+def refuse_fp8_upsample(policy, where: str) -> None:
+    """ValueError when a precision_policy asks for fp8 VAE up-sampling convolutions outside the fp8 tier."""
+    if isinstance(policy, dict) and isinstance(policy.get("vae"), dict) and "fp8_upsample" in policy["vae"]:
+        raise ValueError(f"vae fp8_upsample belongs to OMGSR-F's fp8 tier (weight_dtype=torch.float8_e4m3fn), not to {where}")
 
 
 def set_mx(model: nn.Module, patterns: Iterable[str]) -> int:

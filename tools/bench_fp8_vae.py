@@ -13,7 +13,16 @@
     per arm by timing variant (21 / 22 / others). With --quality: the seeded full-depth draws above with both VAEs tiled (encoder tile 512,
     decoder tile 64), the fp8 tier with and without the key (default list) against the accurate tier.
 
+  * upsample (--upsample; nothing else runs; writes profiles/fp8_vae_upsample.json): precision_policy {"vae": {"fp8_upsample": ...}} on against
+    off, every timed step kept (the acceptance rule of DESIGN 3.1: every step of the on arm faster than every step of the off arm) -
+    per layer, the decoder's three up-sampler shapes at batch 8 (low-resolution maps 128^2 / 256^2 / 512^2 with 512 / 512 / 256 channels): the
+    16-bit phase form against quantize_mxfp8 + mxfp8_conv_up_kernel (the quantise pass counted, and timed alone too); the untiled 1024^2 decode
+    and the tiled decode (decoder tile 64) of the {"fp8": True} VAE with the key on against off. 3 alternated rounds x 3 steps, HIP events.
+    --baseline-repo PATH: a checkout of the PARENT commit with its library built - its decode and tiled decode ({"fp8": True}) are timed by a
+    fresh child process started there, in front of this build's legs, in the same visit.
+
     python tools/bench_fp8_vae.py [--rounds 3] [--no-step] [--quality] [--tiled] [--out profiles/fp8_vae.json]
+    python tools/bench_fp8_vae.py --upsample [--baseline-repo PATH] [--out profiles/fp8_vae_upsample.json]
 """
 from __future__ import annotations
 
@@ -174,7 +183,7 @@ def quality(dev, draws: int) -> list:
     return rows
 
 
-def _variant_counts(fn) -> dict:
+def _variant_counts(fn, variants=(21, 22)) -> dict:
     """Kind-1 (conv / GEMM) launches of one fn() call by timing variant: {"21": n, "22": n, "others": n}, and the number of layers they stand for."""
     import torch
     from omgsr_amd import _lib
@@ -189,7 +198,7 @@ def _variant_counts(fn) -> dict:
     finally:
         lib.omgsr_timing_enable(0)
     v = [e.variant for e in buf[:n] if e.kind == 1]
-    return {"21": v.count(21), "22": v.count(22), "others": len(v) - v.count(21) - v.count(22)}
+    return {**{str(k): v.count(k) for k in variants}, "others": len(v) - sum(v.count(k) for k in variants)}
 
 
 def tiled_decode(dev, batch: int, rounds: int, iters: int) -> dict:
@@ -271,6 +280,136 @@ def tiled_quality(dev, draws: int) -> list:
     return rows
 
 
+# ---- --upsample ----------------------------------------------------------------------------------------------------------------------------
+# (low-resolution map side, channels) of decoder.up_blocks.{0, 1, 2}.upsamplers.0.conv at 1024^2
+UP_SHAPES = [(128, 512), (256, 512), (512, 256)]
+
+
+def _alternate(arms: dict, rounds: int, steps: int, before=None) -> dict:
+    """{arm: [ms of every timed step]}: `rounds` alternated rounds of `steps` single timed calls per arm (before(arm) switches the arm, then one
+    untimed call)."""
+    t = {k: [] for k in arms}
+    for r in range(rounds):
+        for k in (list(arms) if r % 2 == 0 else list(arms)[::-1]):
+            if before is not None:
+                before(k)
+            arms[k]()
+            for _ in range(steps):
+                t[k].append(round(_events_ms(arms[k], 1), 4))
+    return t
+
+
+def _verdict(off, on) -> dict:
+    return dict(speedup_median=round(statistics.median(off) / statistics.median(on), 3), every_on_step_faster_than_every_off_step=max(on) < min(off))
+
+
+def upsample_layers(dev, batch: int, rounds: int, steps: int) -> list:
+    import torch
+    from omgsr_amd import ops
+    rows = []
+    for side, ch in UP_SHAPES:
+        g = torch.Generator(device=dev).manual_seed(side + ch)
+        x = torch.randn(batch, side, side, ch, generator=g, device=dev).to(torch.bfloat16)
+        w = (torch.randn(ch, ch, 3, 3, generator=g, device=dev) / (3.0 * ch ** 0.5)).to(torch.bfloat16)
+        b = torch.zeros(ch, device=dev)
+        p16 = ops.pack_conv_weight(w, b, cout_multiple=8, upsample_phases=True)
+        p8 = ops.pack_conv_weight_mxfp8_up(w, b)
+        arms = {"bf16_phase_form": lambda: ops.conv2d(x, p16, upsample=True, gn_groups=32),
+                "quantize_plus_mxfp8_up": lambda: ops.conv2d(x, p16, upsample=True, gn_groups=32, fp8_up_pack=lambda: p8),
+                "quantize_only": lambda: ops.quantize_mxfp8(x)}
+        for fn in arms.values():
+            fn(); fn()
+        counts = _variant_counts(arms["quantize_plus_mxfp8_up"], (25,))
+        t = _alternate(arms, rounds, steps)
+        fl = 2.0 * batch * 4 * side * side * 9 * ch * ch          # algorithmic (nine taps on the up-sampled map); the phase form runs 4 / 9 of it
+        row = dict(low_res_side=side, channels=ch, batch=batch, served=counts["25"] == 1, ms=t,
+                   bf16_tflops=round(fl / statistics.median(t["bf16_phase_form"]) / 1e9, 1),
+                   mxfp8_conv_alone_tflops=round(fl / (statistics.median(t["quantize_plus_mxfp8_up"]) - statistics.median(t["quantize_only"])) / 1e9, 1),
+                   **_verdict(t["bf16_phase_form"], t["quantize_plus_mxfp8_up"]))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del x, w, p16, p8
+        torch.cuda.empty_cache()
+    return rows
+
+
+# What a checkout WITHOUT the key can run (the parent commit): the {"fp8": True} VAE's untiled and tiled decode, every step's time as JSON.
+_BASELINE_CHILD = r"""
+import json, sys, torch
+sys.path.insert(0, ".")
+from omgsr_amd import _lib, ops
+from omgsr_amd.diffusers_api import AutoencoderKL, FLUX_VAE_CONFIG
+from omgsr_amd.pipelines.vaehook import VAEHook
+from omgsr_amd.precision import set_fp8_conv
+from omgsr_amd.testing import seeded_init_
+batch, rounds, steps = (int(v) for v in sys.argv[1:4])
+dev = torch.device("cuda", 0)
+_lib.check(_lib.load().omgsr_check_device(), "omgsr_check_device")
+ops.set_compute_dtype(torch.bfloat16)
+vae = seeded_init_(AutoencoderKL(**FLUX_VAE_CONFIG), 303, rounded=False).to(dev, torch.bfloat16).eval()
+set_fp8_conv(vae, True)
+hook = VAEHook(vae.decoder, 64, is_decoder=True, fast_decoder=False, fast_encoder=False, color_fix=False)
+hook.fp8_convs = True
+z = torch.randn(batch, 128, 128, 16, generator=torch.Generator().manual_seed(77)).to(dev, torch.bfloat16)
+def ms(fn):
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(); fn(); b.record(); torch.cuda.synchronize()
+    return round(a.elapsed_time(b), 4)
+out = {}
+with torch.no_grad():
+    for name, fn in (("decode", lambda: vae.decode_nhwc(z)), ("tiled_decode", lambda: hook(z))):
+        fn(); fn()
+        out[name] = [ms(fn) for _ in range(rounds * steps)]
+print("BASELINE " + json.dumps(out))
+"""
+
+
+def upsample_baseline(repo: str, batch: int, rounds: int, steps: int) -> dict:
+    """The parent commit's build, timed by a fresh child process in its own checkout (its package, its library)."""
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", _BASELINE_CHILD, str(batch), str(rounds), str(steps)], cwd=repo, capture_output=True, text=True, timeout=900)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("BASELINE ")]
+    if r.returncode != 0 or not lines:
+        raise RuntimeError(f"baseline run in {repo} failed ({r.returncode}): {r.stderr[-2000:]}")
+    return json.loads(lines[-1][len("BASELINE "):])
+
+
+def upsample_decodes(dev, batch: int, rounds: int, steps: int) -> dict:
+    """The {"fp8": True} FLUX VAE, 128 x 128 latent: untiled decode and tiled decode (decoder tile 64, fp8_convs hooks), fp8_upsample on against off."""
+    import torch
+    from omgsr_amd.diffusers_api import AutoencoderKL, FLUX_VAE_CONFIG
+    from omgsr_amd.pipelines.vaehook import VAEHook
+    from omgsr_amd.precision import clear_fp8_upsample, set_fp8_conv, set_fp8_upsample
+    from omgsr_amd.testing import seeded_init_
+    vae = seeded_init_(AutoencoderKL(**FLUX_VAE_CONFIG), 303, rounded=False).to(dev, torch.bfloat16).eval()
+    set_fp8_conv(vae, True)
+    hook = VAEHook(vae.decoder, 64, is_decoder=True, fast_decoder=False, fast_encoder=False, color_fix=False)
+    hook.fp8_convs = True
+    z = torch.randn(batch, 128, 128, 16, generator=torch.Generator().manual_seed(77)).to(dev, torch.bfloat16)
+
+    def switch(arm):
+        if arm == "on":
+            set_fp8_upsample(vae, True)
+        else:
+            clear_fp8_upsample(vae)
+
+    out = {}
+    with torch.no_grad():
+        for name, fn in (("decode", lambda: vae.decode_nhwc(z)), ("tiled_decode", lambda: hook(z))):
+            arms = {"off": fn, "on": fn}
+            counts = {}
+            for k in arms:
+                switch(k)
+                fn(); fn()                              # warm: packs, code objects
+                counts[k] = _variant_counts(fn, (21, 22, 25, 26))
+            t = _alternate(arms, rounds, steps, before=switch)
+            out[name] = dict(ms=t, kind1_launches_by_variant=counts, **_verdict(t["off"], t["on"]))
+            print(name, json.dumps(out[name]), flush=True)
+    clear_fp8_upsample(vae)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=3)
@@ -282,8 +421,12 @@ def main():
     ap.add_argument("--draws", type=int, default=3)
     ap.add_argument("--tiled", action="store_true", help="the tiled VAE decode legs only (with --quality: the tiled full-depth draws)")
     ap.add_argument("--iters", type=int, default=5, help="--tiled: decodes per timed window")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp8_vae.json"))
+    ap.add_argument("--upsample", action="store_true", help="the fp8_upsample legs only (default --out profiles/fp8_vae_upsample.json)")
+    ap.add_argument("--baseline-repo", default=None, help="--upsample: a checkout of the parent commit with its library built, timed first")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "fp8_vae_upsample.json" if args.upsample else "fp8_vae.json")
     import torch
     from omgsr_amd import _lib, ops
     dev = torch.device("cuda", 0)
@@ -293,6 +436,19 @@ def main():
     if os.path.isfile(args.out):                    # sections measured by an earlier call stay
         with open(args.out) as f:
             rec = {**json.load(f), **rec}
+    if args.upsample:
+        if args.baseline_repo:
+            rec["parent_build_fp8_true_b%d" % args.batch] = dict(ms=upsample_baseline(args.baseline_repo, args.batch, args.rounds, args.steps))
+            print(json.dumps(rec["parent_build_fp8_true_b%d" % args.batch]), flush=True)
+        rec["layers_b%d" % args.batch] = upsample_layers(dev, args.batch, args.rounds, args.steps)
+        rec["decodes_b%d" % args.batch] = upsample_decodes(dev, args.batch, args.rounds, args.steps)
+        base = rec.get("parent_build_fp8_true_b%d" % args.batch)
+        if base:                                        # the same rule against the parent's build, run just before
+            for name, d in rec["decodes_b%d" % args.batch].items():
+                d["against_parent_build"] = _verdict(base["ms"][name], d["ms"]["on"])
+                d["off_arm_against_parent_build"] = dict(median_ratio=round(statistics.median(d["ms"]["off"]) / statistics.median(base["ms"][name]), 3))
+        args.no_layers = args.no_step = True
+        args.quality = args.tiled = False
     if args.tiled:
         rec["tiled_decode_b%d" % args.batch] = tiled_decode(dev, args.batch, args.rounds, args.iters)
         print(json.dumps(rec["tiled_decode_b%d" % args.batch]), flush=True)
