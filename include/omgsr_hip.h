@@ -250,6 +250,15 @@ int omgsr_conv_mxfp8(const omgsr_igemm_args* a, void* stream);
  * mode; the entry points put it there themselves, whatever the field held). */
 int32_t omgsr_conv_mxfp8_multi_ok(const omgsr_igemm_args* args, int32_t count);
 int omgsr_conv_mxfp8_multi(const omgsr_igemm_args* args, int32_t count, void* stream);
+/* Additive under ABI v22 (no struct changed): the deep-K form of omgsr_conv_mxfp8 (mxfp8_conv_deep_kernel: OMGSR-S's opt-in UNet resnet convs
+ * on the bf16 tier). The same argument block, operand and weight layouts (Cin / 64 chunks, Cin / 32 scale bytes per pixel - an even count, so
+ * a scale row is only 2-byte aligned) and output options. The kernel stages the operand scales per 64-channel chunk and reads nothing wider
+ * than one chunk's byte pair, so no byte past either plane is touched.
+ * omgsr_conv_mxfp8_deep_ok: omgsr_conv_mxfp8_ok's rules with Cin % 64 == 0 and Cin <= 2048 in place of Cin % 128 == 0 and Cin <= 512 (and
+ * H W Cin / 32 < 2^31). omgsr_conv_mxfp8_deep returns OMGSR_E_SHAPE for anything else (never another kernel). The two entry points above keep
+ * every answer they gave: a problem both predicates accept may go to either. */
+int32_t omgsr_conv_mxfp8_deep_ok(const omgsr_igemm_args* a);
+int omgsr_conv_mxfp8_deep(const omgsr_igemm_args* a, void* stream);
 /* Additive under ABI v22 (no struct changed): the MXFP8 form of nearest-2x up-sampling + 3x3 stride-1 pad-1 convolution (mxfp8_conv_up_kernel: the
  * fp8 tier's opt-in VAE up-samplers), as four 2 x 2 convolutions of the LOW-resolution map. The argument block of the same omgsr_igemm problem
  * (upsample = 1, Ho = 2 H, Wo = 2 W) with
@@ -373,6 +382,11 @@ int omgsr_groupnorm_apply_multi(const omgsr_gn_apply_group* groups, int32_t ngro
 int omgsr_groupnorm_apply_mxfp8(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma,
                                 const float* beta, int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
                                 int32_t x_el, void* stream);
+/* Additive under ABI v22: omgsr_groupnorm_apply_mxfp8 (the same kernel, the same bytes) for C % 64 == 0 - the operand of omgsr_conv_mxfp8_deep.
+ * C / G need not be a multiple of 8: a thread's octet and a 32-channel block may straddle groups (C = 320, G = 32). */
+int omgsr_groupnorm_apply_mxfp8_c64(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma,
+                                    const float* beta, int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                    int32_t x_el, void* stream);
 /* Additive under ABI v22: omgsr_groupnorm_apply_mxfp8 over up to OMGSR_GN_MAX_GROUPS tensors of one channel count and element kind in ONE
  * launch (gn_apply_mxfp8_multi_kernel; the groups of omgsr_groupnorm_apply_multi with y = codes, y2 = scales, both set). Row r of every tensor
  * uses the statistics of image r % stat_rows; the bytes written equal those of one omgsr_groupnorm_apply_mxfp8 call per tensor. */
@@ -598,7 +612,8 @@ int omgsr_timing_reset(void);
  * (OMGSR_EL_MX6) correction chunks: single, launch group, split-K, 16 / 17 the same in the phase-decomposed form: single, launch group,
  * 18 mxfp8_gemm_kernel (ABI v18), 21 mxfp8_conv_kernel (ABI v22), 22 mxfp8_conv_multi_kernel (several problems of one layer in one launch),
  * 24 mxfp8_gemm_multi_kernel (up to 4 independent MXFP8 GEMMs in one launch: omgsr_igemm_mxfp8_multi), 25 mxfp8_conv_up_kernel (nearest-2x
- * up-sampling + 3x3 conv in MXFP8, phase-decomposed), 26 mxfp8_conv_up_multi_kernel (several problems of one layer in one launch).
+ * up-sampling + 3x3 conv in MXFP8, phase-decomposed), 26 mxfp8_conv_up_multi_kernel (several problems of one layer in one launch),
+ * 27 mxfp8_conv_deep_kernel (the MXFP8 3x3 conv with staged operand scales: Cin % 64 == 0 up to 2048).
  * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19), 20 vae_attn_kernel (ABI v20, D = 512), 23 vae_attn_full_kernel (D = 512, every operand a two-term split). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;

@@ -108,7 +108,10 @@ SIGNATURES = {
     "omgsr_conv_mxfp8_up": (C.c_int, [C.POINTER(IgemmArgs), _P]),
     "omgsr_conv_mxfp8_up_multi_ok": (C.c_int32, [C.POINTER(IgemmArgs), _I]),
     "omgsr_conv_mxfp8_up_multi": (C.c_int, [C.POINTER(IgemmArgs), _I, _P]),
+    "omgsr_conv_mxfp8_deep_ok": (C.c_int32, [C.POINTER(IgemmArgs)]),
+    "omgsr_conv_mxfp8_deep": (C.c_int, [C.POINTER(IgemmArgs), _P]),
     "omgsr_groupnorm_apply_mxfp8": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P]),
+    "omgsr_groupnorm_apply_mxfp8_c64": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _P]),
     "omgsr_groupnorm_apply_mxfp8_multi": (C.c_int, [C.POINTER(GnApplyGroup), _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "omgsr_groupnorm_scale_shift": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "omgsr_groupnorm_finalize": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, C.c_double, _F, _P]),

@@ -838,6 +838,38 @@ extern "C" int omgsr_conv_mxfp8_up_multi(const omgsr_igemm_args* args, int32_t c
     return 0;
 }
 
+// ---- additive under ABI v22: the deep-K form of the MXFP8 3x3 convolution (conv_mxfp8_deep.hip) ------------------------------------------
+namespace {
+// Served: conv_mxfp8_ok's rules with Cin % 64 == 0, Cin <= 2048 - what mxfp8_conv_deep_kernel runs AND the geometry for which this
+// dispatcher hands the bf16 problem to the halo-tile kernel's spatial nine-tap form (tile-count policy included, one sample's rows in
+// batch-invariant mode): the fp8 form replaces that launch, nothing else
+bool conv_mxfp8_deep_ok(omgsr_igemm_args a) {
+    if (a.in_ld == a.Cin) a.in_ld = 0;
+    if (!omgsr::mxfp8_conv_deep_shape_ok(a)) return false;
+    if ((int64_t)a.H * a.W * (a.Cin / 32) >= (int64_t)1 << 31) return false;
+    if (!a.weight_cm) a.weight_cm = &a;             // (the answer does not depend on the pointers: the host asks before it packs)
+    a.workspace = nullptr;
+    return use_halo(a) && !use_halo_phase(a) && omgsr::igemm_halo_flat(a) == 0;
+}
+}  // namespace
+
+extern "C" int32_t omgsr_conv_mxfp8_deep_ok(const omgsr_igemm_args* ap) { return (ap && conv_mxfp8_deep_ok(*ap)) ? 1 : 0; }
+
+extern "C" int omgsr_conv_mxfp8_deep(const omgsr_igemm_args* ap, void* stream) {
+    if (!ap) return OMGSR_E_BADARG;
+    omgsr_igemm_args a = *ap;
+    if (!a.weight) a.weight = a.weight_cm;          // (the row-major packing does not exist in this form)
+    if (!a.in_scale || !a.w_scale || !a.weight_cm) return OMGSR_E_BADARG;
+    {
+        const int rc = validate_args(a);
+        if (rc != 0) return rc;
+    }
+    if (!conv_mxfp8_deep_ok(a)) return OMGSR_E_SHAPE;
+    double flops, bytes;
+    work_of(a, &flops, &bytes);
+    return omgsr::mxfp8_conv_deep_launch(a, geo_of(a), (hipStream_t)stream, flops);
+}
+
 // Additive under ABI v22: an mxf8 problem whose output is written in the OMGSR_EL_MXFP8 form (include/omgsr_hip.h) - mxfp8_gemm_kernel's OUT8
 // instantiation or nothing. The scale plane travels next to the argument block, whose layout does not change.
 extern "C" int omgsr_igemm_out_mxfp8(const omgsr_igemm_args* ap, void* out_scale, int64_t out_scale_ld, void* stream) {

@@ -23,6 +23,8 @@ int mxfp8_conv_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int c
 bool mxfp8_conv_up_shape_ok(const omgsr_igemm_args& a);                                                         // conv_mxfp8_up.hip
 int mxfp8_conv_up_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, double flops);
 int mxfp8_conv_up_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int count, hipStream_t st, double flops);
+bool mxfp8_conv_deep_shape_ok(const omgsr_igemm_args& a);                                                       // conv_mxfp8_deep.hip
+int mxfp8_conv_deep_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, double flops);
 
 // ---- halo-tile kernel: what the dispatcher asks and calls (igemm_halo.hip, igemm_halo_multi.hip) ------------------------------------
 int igemm_halo_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, bool phase = false);

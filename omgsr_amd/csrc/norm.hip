@@ -1074,12 +1074,13 @@ int gn_apply_launch(const void* x, void* y, const float* mean, const float* rstd
 }
 }  // namespace
 
-extern "C" int omgsr_groupnorm_apply_mxfp8(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma,
-                                           const float* beta, int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
-                                           int32_t x_el, void* stream) {
+namespace {
+// The two entry points below differ in the channel multiple they accept (`cmult`); gn_apply_mxfp8_body itself takes any C % 32 == 0.
+int gn_apply_mxfp8_launch(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                          int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows, int32_t x_el, int32_t cmult, void* stream) {
     if (!x || !codes || !scales || !mean || !rstd || rows <= 0 || HW <= 0 || C <= 0 || G <= 0 || stat_rows <= 0 || (rows % stat_rows)) return OMGSR_E_BADARG;
     if ((x_el != OMGSR_EL_16 && x_el != OMGSR_EL_F32) || (act != OMGSR_ACT_NONE && act != OMGSR_ACT_SILU)) return OMGSR_E_BADARG;
-    if ((C % 128) || (C % G) || C > 8192 || omgsr::compute_dtype() != 0) return OMGSR_E_SHAPE;      // the format's K % 128; a 16-bit x is bf16
+    if ((C % cmult) || (C % G) || C > 8192 || omgsr::compute_dtype() != 0) return OMGSR_E_SHAPE;      // the consumer's K rule; a 16-bit x is bf16
     hipStream_t st = (hipStream_t)stream;
     const int64_t ppb = gn_apply_ppb(rows, HW, C);
     const dim3 grid((unsigned)((HW + ppb - 1) / ppb), rows);
@@ -1091,6 +1092,21 @@ extern "C" int omgsr_groupnorm_apply_mxfp8(const void* x, void* codes, void* sca
         hipLaunchKernelGGL(gn_apply_mxfp8_kernel<false>, grid, dim3(256), 2 * C * sizeof(float), st, x, (unsigned char*)codes, (unsigned char*)scales, mean, rstd, gamma,
                            beta, HW, (int)C, (int)G, (int)act, ppb, (int)stat_rows);
     return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int omgsr_groupnorm_apply_mxfp8(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma,
+                                           const float* beta, int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                           int32_t x_el, void* stream) {
+    return gn_apply_mxfp8_launch(x, codes, scales, mean, rstd, gamma, beta, rows, HW, C, G, act, stat_rows, x_el, 128, stream);     // the format's K % 128
+}
+
+// Additive under ABI v22: the same kernel for the operand of omgsr_conv_mxfp8_deep (C % 64 == 0: whole 64-channel chunks). With C / G not a
+// multiple of 8 or 32 a thread's octet and a block straddle groups; the per-channel (scale, shift) table in LDS serves that as it is.
+extern "C" int omgsr_groupnorm_apply_mxfp8_c64(const void* x, void* codes, void* scales, const float* mean, const float* rstd, const float* gamma,
+                                               const float* beta, int32_t rows, int64_t HW, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
+                                               int32_t x_el, void* stream) {
+    return gn_apply_mxfp8_launch(x, codes, scales, mean, rstd, gamma, beta, rows, HW, C, G, act, stat_rows, x_el, 64, stream);
 }
 
 extern "C" int omgsr_groupnorm_apply_mxfp8_multi(const omgsr_gn_apply_group* groups, int32_t ngroups, const float* mean, const float* rstd,

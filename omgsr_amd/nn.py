@@ -170,6 +170,24 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
         self._pk8u, self._pk8u_key = None, None
         bump_cache_epoch()
 
+    # OMGSR-S's bf16 tier (precision.set_fp8_unet_conv): a UNet resnet conv whose problems the library serves (ops.conv2d fp8_deep_pack) runs as
+    # mxfp8_conv_deep_kernel behind the GroupNorm apply pass that writes MXFP8; the same layout as packed_mxfp8 with whole 64-channel chunks
+    # (Cin = 320 ... 1920), packed lazily under its own key
+    fp8_deep = False
+
+    def packed_mxfp8_deep(self) -> ops.PackedWeight:
+        k = _key(self.weight, self.bias, "mxfp8-conv-deep")
+        if getattr(self, "_pk8d_key", None) != k:
+            bump_cache_epoch()
+            _log_rebuild(self._drop_packed_mxfp8_deep)
+            self._pk8d = ops.pack_conv_weight_mxfp8(self.weight, self.bias, cin_multiple=64)
+            self._pk8d_key = k
+        return self._pk8d
+
+    def _drop_packed_mxfp8_deep(self) -> None:
+        self._pk8d, self._pk8d_key = None, None
+        bump_cache_epoch()
+
     def packed(self) -> ops.PackedWeight:
         # logical Cout widened to a multiple of 8 (zero rows): 3/4-channel heads write 16-byte NHWC rows
         sp, wsp, ph = self.in_split(), self.in_wsplit(), self.phase_upsample
@@ -189,8 +207,14 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
             out_dtype = ops.OUT_BF16
         fp8_pack = self.packed_mxfp8 if (self.fp8 and gn is not None and bias_override is None) else None
         fp8_up_pack = self.packed_mxfp8_up if (self.fp8_up and upsample and gn is None and bias_override is None) else None
+        fp8_deep_pack = None
+        if self.fp8_deep and gn is not None and self.in_channels % 64 == 0:
+            # (the UNet's conv1 carries the folded time embedding as bias_override: it rides the MXFP8 pack as it rides the bf16 one)
+            fp8_deep_pack = self.packed_mxfp8_deep if bias_override is None else \
+                (lambda: dataclasses.replace(self.packed_mxfp8_deep(), bias=bias_override))
         return ops.conv2d(x, pw, stride=stride or self.stride[0], pad=p, upsample=upsample, act=act, residual=residual,
-                          gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack, fp8_up_pack=fp8_up_pack)
+                          gn_groups=gn_groups, out_dtype=out_dtype, out_split=out_split, gn=gn, fp8_pack=fp8_pack, fp8_up_pack=fp8_up_pack,
+                          fp8_deep_pack=fp8_deep_pack)
 
     def nhwc_multi(self, xs, *, pad=None, upsample=False, act=ops.ACT_NONE, residuals=None, stride=None, gn_groups=0,
                    out_dtype=ops.OUT_STREAM, out_split=1, gn=None, fp8=False):

@@ -677,22 +677,29 @@ def _fill_mxfp8(a: IgemmArgs, codes_ptr: int, scales_ptr: int, pw: PackedWeight)
     _fill_taps_1x1(a)
 
 
-def pack_conv_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> PackedWeight:
+def pack_conv_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None, cin_multiple: int = 128) -> PackedWeight:
     """[Cout, Cin, 3, 3] bf16 -> the weight of omgsr_conv_mxfp8 (include/omgsr_hip.h): one MXFP8 block per 32 consecutive input channels of
     one (cout, ky, kx), quantised on the device by quantize_mxfp8 (rows = (cout, tap), K = Cin), then laid out slice-major:
     `w_cm` codes uint8 [Cin/64][9][Cout_pad][64], `w_scale` uint8 [Cin/64][Cout_pad][2][16] (byte t < 9 = tap t). Rows are padded with zeros
-    to a multiple of 128; `w` is the codes tensor too (the row-major packing does not exist in this form)."""
+    to a multiple of 128; `w` is the codes tensor too (the row-major packing does not exist in this form).
+    cin_multiple=64: the same layout for omgsr_conv_mxfp8_deep (whole 64-channel chunks; nothing in the layout needs more). quantize_mxfp8
+    wants K % 128 == 0, so the rows are quantised with Cin padded by zero channels - blocks are independent, the padding's are dropped."""
     if _PRECISE or _ACT != torch.bfloat16:
         raise ValueError("an fp8 (MXFP8) layer needs the bf16 compute type (the fp8 tier); the accurate tier and fp16 have none")
     dev = device or weight.device
     cout, cin, R, S = weight.shape
-    if (R, S) != (3, 3) or cin % 128:
-        raise ValueError(f"an fp8 (MXFP8) conv needs a 3x3 kernel and in_channels % 128 == 0, got {tuple(weight.shape)}")
+    if cin_multiple not in (64, 128):
+        raise ValueError(f"pack_conv_weight_mxfp8: cin_multiple is 128 (omgsr_conv_mxfp8) or 64 (omgsr_conv_mxfp8_deep), got {cin_multiple}")
+    if (R, S) != (3, 3) or cin % cin_multiple:
+        raise ValueError(f"an fp8 (MXFP8) conv needs a 3x3 kernel and in_channels % {cin_multiple} == 0, got {tuple(weight.shape)}")
     cout8 = _round_up(cout, 8)
     cout_pad = _round_up(cout8, 128)
-    w = torch.zeros((cout_pad, 9, cin), device=dev, dtype=torch.bfloat16)
-    w[:cout] = weight.detach().to(device=dev, dtype=torch.bfloat16).permute(0, 2, 3, 1).reshape(cout, 9, cin)
+    cin_q = _round_up(cin, 128)
+    w = torch.zeros((cout_pad, 9, cin_q), device=dev, dtype=torch.bfloat16)
+    w[:cout, :, :cin] = weight.detach().to(device=dev, dtype=torch.bfloat16).permute(0, 2, 3, 1).reshape(cout, 9, cin)
     q = quantize_mxfp8(w)
+    if cin_q != cin:
+        q = Mxfp8(q.codes[..., :cin].contiguous(), q.scales[..., :cin // 32].contiguous())
     codes = q.codes.view(cout_pad, 9, cin // 64, 64).permute(2, 1, 0, 3).contiguous()                 # [chunk][tap][cout][64]
     sc = torch.zeros((cin // 64, cout_pad, 2, 16), device=dev, dtype=torch.uint8)
     sc[..., :9] = q.scales.view(cout_pad, 9, cin // 64, 2).permute(2, 0, 3, 1)                          # [chunk][cout][block][tap]
@@ -966,7 +973,7 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: tuple[int
            upsample: bool = False, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
            gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM, alpha: float = 1.0,
            out: Optional[torch.Tensor] = None, gn_groups: int = 0, out_split: int = 1, sample_rows: int = 0,
-           gn: Optional["GnSpec"] = None, fp8_pack=None, fp8_up_pack=None) -> torch.Tensor:
+           gn: Optional["GnSpec"] = None, fp8_pack=None, fp8_up_pack=None, fp8_deep_pack=None) -> torch.Tensor:
     """x [N,H,W,Cin] operand (or a stream tensor: cast / split here) -> [N,Ho,Wo,Cout]. pad = (top, bottom, left, right) on
     the (virtual) input. out_dtype: OUT_STREAM (a stream tensor: default), OUT_BF16 (a 16-bit operand for the next GEMM,
     `out_split` 2 = written as the two-term split) or OUT_F32. residual: a stream tensor of the output's shape.
@@ -979,13 +986,21 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: tuple[int
     writes MXFP8 and mxfp8_conv_kernel runs the conv; otherwise the call takes the 16-bit path below exactly as without it.
     fp8_up_pack (upsample=True on a layer marked by precision.set_fp8_upsample; no gn, no residual): a callable returning the layer's
     pack_conv_weight_mxfp8_up form. Where omgsr_conv_mxfp8_up_ok accepts the problem, x goes through quantize_mxfp8 (one pass over the
-    low-resolution map) and mxfp8_conv_up_kernel runs the conv; otherwise the call takes the 16-bit path below exactly as without it."""
+    low-resolution map) and mxfp8_conv_up_kernel runs the conv; otherwise the call takes the 16-bit path below exactly as without it.
+    fp8_deep_pack (a layer marked by precision.set_fp8_unet_conv; needs gn): a callable returning the layer's
+    pack_conv_weight_mxfp8(cin_multiple=64) form. Where omgsr_conv_mxfp8_deep_ok accepts the problem, the GroupNorm runs as the apply pass that
+    writes MXFP8 (group_norm_apply_mxfp8 with c64) and mxfp8_conv_deep_kernel runs the conv; otherwise the call takes the 16-bit path below
+    exactly as without it. The deep kernel serves everything omgsr_conv_mxfp8_ok accepts too, so a layer with this mark never needs the other
+    pack. (Every shape of the UNet's served levels is faster this way in every timed step, DESIGN.md 3.5: none is held back by shape.)"""
     a = IgemmArgs()
     if gn is not None and not _gn_candidate(x, pw):
         x, gn = gn.apply(x, pw.split), None
     x, out = _conv_args(a, x, pw, stride, pad, upsample, act, residual, gate, out_dtype, alpha, out, out_split, sample_rows)
     if fp8_pack is not None and gn is not None and out_split == 1 and _lib.load().omgsr_conv_mxfp8_ok(C.byref(a)):
         return _conv2d_mxfp8(a, gn.apply(x, 5), fp8_pack(), out, gn_groups)
+    if fp8_deep_pack is not None and gn is not None and out_split == 1 and _lib.load().omgsr_conv_mxfp8_deep_ok(C.byref(a)):
+        xq = group_norm_apply_mxfp8(x, gn.mean, gn.rstd, gn.gamma, gn.beta, gn.groups, gn.act, c64=True)
+        return _conv2d_mxfp8(a, xq, fp8_deep_pack(), out, gn_groups, deep=True)
     if (fp8_up_pack is not None and upsample and gn is None and residual is None and out_split == 1
             and _lib.load().omgsr_conv_mxfp8_up_ok(C.byref(a))):
         return _conv2d_mxfp8_up(a, quantize_mxfp8(x), fp8_up_pack(), out, gn_groups)
@@ -1010,14 +1025,18 @@ def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: tuple[int
     return out
 
 
-def _conv2d_mxfp8(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight, out: torch.Tensor, gn_groups: int) -> torch.Tensor:
-    """Launch omgsr_conv_mxfp8 on an argument block filled for the 16-bit form of the same problem (geometry, epilogue, output)."""
+def _conv2d_mxfp8(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight, out: torch.Tensor, gn_groups: int, deep: bool = False) -> torch.Tensor:
+    """Launch omgsr_conv_mxfp8 (deep: omgsr_conv_mxfp8_deep) on an argument block filled for the 16-bit form of the same problem (geometry,
+    epilogue, output)."""
     if xq.codes.shape[-1] != pw8.cin or a.Cout != pw8.cout:
         raise ValueError(f"conv2d_mxfp8: operand K {xq.codes.shape[-1]} / Cout {a.Cout} do not match the packed weight ({pw8.cin}, {pw8.cout})")
     a.in_, a.in_scale = xq.codes.data_ptr(), xq.scales.data_ptr()
     _fill_conv_mxfp8(a, pw8)
     partial = _conv_gn(a, gn_groups, 1, out.device)
-    check(_lib.load().omgsr_conv_mxfp8(C.byref(a), _stream()), "omgsr_conv_mxfp8")
+    if deep:
+        check(_lib.load().omgsr_conv_mxfp8_deep(C.byref(a), _stream()), "omgsr_conv_mxfp8_deep")
+    else:
+        check(_lib.load().omgsr_conv_mxfp8(C.byref(a), _stream()), "omgsr_conv_mxfp8")
     if partial is not None:
         _leave_gn(out, partial, gn_groups)
     return out
@@ -1038,15 +1057,17 @@ def _conv_mxfp8_args(a: IgemmArgs, xq: "Mxfp8", pw8: PackedWeight, act: int, res
 
 
 def conv2d_mxfp8(xq: "Mxfp8", pw8: PackedWeight, *, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None,
-                 gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM, gn_groups: int = 0, sample_rows: int = 0) -> torch.Tensor:
+                 gate: Optional[torch.Tensor] = None, out_dtype: int = OUT_STREAM, gn_groups: int = 0, sample_rows: int = 0,
+                 deep: bool = False) -> torch.Tensor:
     """3x3 stride-1 pad-1 conv of an MXFP8 operand xq [N,H,W,Cin] (quantize_mxfp8 / group_norm_apply split 5) with a pack_conv_weight_mxfp8
-    weight -> [N,H,W,Cout8]. No other kernel stands behind it: a problem omgsr_conv_mxfp8_ok does not accept raises (OMGSR_E_SHAPE)."""
+    weight -> [N,H,W,Cout8]. No other kernel stands behind it: a problem omgsr_conv_mxfp8_ok does not accept raises (OMGSR_E_SHAPE).
+    deep: through omgsr_conv_mxfp8_deep (mxfp8_conv_deep_kernel: Cin % 64 == 0 up to 2048, a cin_multiple=64 pack) under the same rule."""
     if not isinstance(xq, Mxfp8) or not pw8.fp8 or pw8.w_cm is None:
         raise ValueError("conv2d_mxfp8: an Mxfp8 operand and a pack_conv_weight_mxfp8 weight")
     a = IgemmArgs()
     out = _conv_mxfp8_args(a, xq, pw8, act, residual, out_dtype, sample_rows)
     a.gate = _ptr(gate)
-    return _conv2d_mxfp8(a, xq, pw8, out, gn_groups)
+    return _conv2d_mxfp8(a, xq, pw8, out, gn_groups, deep=deep)
 
 
 def _mxfp8_group_tiles(arr, n: int) -> int:
@@ -1655,18 +1676,22 @@ def _group_norm_apply(x, mean, rstd, gamma, beta, groups: int, act: int, inplace
     return (y, y2) if also_cast else y
 
 
-def group_norm_apply_mxfp8(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE) -> "Mxfp8":
+def group_norm_apply_mxfp8(x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE,
+                           c64: bool = False) -> "Mxfp8":
     """Stream tensor x [rows, ..., C] (bf16 or fp32, read only) -> act(GroupNorm(x)) as an Mxfp8 [rows, ..., C]: the fp32 result of the apply
     arithmetic quantised by quantize_mxfp8's rule in the same pass (omgsr_groupnorm_apply_mxfp8). mean / rstd [N, G]: row r uses the
-    statistics of image r % N. C % 128 == 0, bf16 compute type."""
+    statistics of image r % N. C % 128 == 0, bf16 compute type. c64: C % 64 == 0 through omgsr_groupnorm_apply_mxfp8_c64 (the same kernel; the
+    operand of the deep conv form)."""
     xel = _el(x, "x")
     rows, Cc = x.shape[0], x.shape[-1]
     HW = x.numel() // (rows * Cc)
-    if Cc % 128:
-        raise ValueError(f"group_norm_apply_mxfp8: C = {Cc} is not a multiple of 128")
+    if Cc % (64 if c64 else 128):
+        raise ValueError(f"group_norm_apply_mxfp8: C = {Cc} is not a multiple of {64 if c64 else 128}")
     out = _mxfp8_like(x)
-    check(_lib.load().omgsr_groupnorm_apply_mxfp8(x.data_ptr(), out.codes.data_ptr(), out.scales.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
-                                                  _ptr(beta), rows, HW, Cc, groups, act, mean.shape[0], xel, _stream()), "omgsr_groupnorm_apply_mxfp8")
+    lib = _lib.load()
+    fn, what = (lib.omgsr_groupnorm_apply_mxfp8_c64, "omgsr_groupnorm_apply_mxfp8_c64") if c64 else (lib.omgsr_groupnorm_apply_mxfp8, "omgsr_groupnorm_apply_mxfp8")
+    check(fn(x.data_ptr(), out.codes.data_ptr(), out.scales.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), _ptr(beta), rows, HW, Cc, groups,
+             act, mean.shape[0], xel, _stream()), what)
     return out
 
 

@@ -37,6 +37,22 @@ class OMGSR_S_Infer(torch.nn.Module):
         from ..precision import refuse_fp8_conv, refuse_fp8_upsample
         refuse_fp8_conv(precision_policy, "OMGSR-S")
         refuse_fp8_upsample(precision_policy, "OMGSR-S")
+        # precision_policy={"unet": {"fp8": True | [layer patterns]}} (bf16 tier only, opt-in): those resnet convs of the UNet run as MXFP8
+        # convolutions where the deep-K kernel serves them (precision.set_fp8_unet_conv); checked before anything is loaded
+        from ..precision import check_fp8_unet_conv, refuse_fp8_unet_conv
+        fp8_unet = None
+        if isinstance(precision_policy, dict) and "unet" in precision_policy:
+            u = precision_policy["unet"]
+            if not isinstance(u, dict) or not set(u) <= {"fp8", "act", "weight", "inner16"}:
+                raise ValueError("OMGSR-S's precision_policy['unet'] is {'fp8': True | [layer patterns]} on the bf16 tier, "
+                                 "{'act': [...], 'weight': [...], 'inner16': [...]} on the accurate tier")
+            if weight_dtype != torch.bfloat16:
+                refuse_fp8_unet_conv(precision_policy, f"the {weight_dtype} tier")
+            fp8_unet = u.get("fp8")
+            if fp8_unet is False:
+                fp8_unet = None
+            if fp8_unet is not None:
+                check_fp8_unet_conv(fp8_unet)
         # --weight_dtype picks the tier: bf16 / fp16 = that 16-bit type end to end; fp32 = the accurate tier (fp32 stream
         # tensors, fp16 MFMA operands, two-term split operands where the precision policy says so)
         ops.set_compute_dtype(weight_dtype)
@@ -56,7 +72,12 @@ class OMGSR_S_Infer(torch.nn.Module):
         self.vae = vae.to(device=device, dtype=weight_dtype).eval()
         self.unet = unet.to(device=device, dtype=weight_dtype).eval()
         self.device = device
-        from ..precision import RangeFallback
+        from ..precision import RangeFallback, clear_fp8_unet_conv, set_fp8_unet_conv
+        if fp8_unet is not None:
+            set_fp8_unet_conv(self.unet, fp8_unet)
+        else:
+            clear_fp8_unet_conv(self.unet)
+        self.fp8_unet = fp8_unet is not None
         if weight_dtype == torch.float32:       # which layers carry two-term split operands / weights (omgsr_amd/precision.py)
             from ..precision import resolve
             resolve(precision_policy, vae=self.vae, unet=self.unet)

@@ -438,6 +438,80 @@ def refuse_fp8_upsample(policy, where: str) -> None:
         raise ValueError(f"vae fp8_upsample belongs to OMGSR-F's fp8 tier (weight_dtype=torch.float8_e4m3fn), not to {where}")
 
 
+# The UNet's resnet convolutions on OMGSR-S's bf16 tier (opt-in: precision_policy={"unet": {"fp8": True | [patterns]}}, weight_dtype=bfloat16
+# only): a marked conv runs as mxfp8_conv_deep_kernel - the MXFP8 nine-tap conv with staged operand scales, Cin % 64 == 0 up to 2048 - behind
+# the GroupNorm + SiLU apply pass that writes MXFP8, wherever the library serves the problem (omgsr_conv_mxfp8_deep_ok: the halo-tile
+# kernel's spatial form, i.e. the 64- and 32-wide latent levels at 192 tiles or more); every other problem of a marked layer (the 16- and
+# 8-wide levels, small batches) takes the bf16 path bit for bit. UNET_FP8_ELIGIBLE is the hard limit: the resnet conv1 / conv2 of the down,
+# mid and up blocks, the only convs that read a GroupNorm + SiLU output. UNET_FP8 is what `True` marks: the 20 convs of the two levels the
+# kernel serves at the pipeline's 64 x 64 latent tiles (down_blocks 0-1, up_blocks 2-3). All eight of their shapes are faster in MXFP8 in every
+# timed step (1.37-1.69x, profiles/fp8_unet.json) and the full-depth OMGSR-S 256 -> 1024 output holds 31.2-34.2 dB against the accurate tier
+# on three seeded draws (target >= 30 dB; the bf16 tier alone: 43.7-45.2), DESIGN.md 3.5. The other 24 eligible layers move when named; at
+# the usual tile size their problems are refused and nothing changes.
+UNET_FP8_ELIGIBLE = [r"^(down_blocks\.\d+|mid_block|up_blocks\.\d+)\.resnets\.\d+\.conv[12]$"]
+UNET_FP8 = [r"^(down_blocks\.[01]|up_blocks\.[23])\.resnets\.\d+\.conv[12]$"]
+
+
+def _fp8_unet_candidates(model: nn.Module):
+    elig = [re.compile(p) for p in UNET_FP8_ELIGIBLE]
+    return [(name, m) for name, m in model.named_modules() if isinstance(m, Conv2d) and any(r.search(name) for r in elig)]
+
+
+def check_fp8_unet_conv(patterns) -> list:
+    """The model-independent half of set_fp8_unet_conv: True -> UNET_FP8 (ValueError should it be empty), a non-empty list of strings -> itself,
+    ValueError for anything else."""
+    if patterns is True:
+        if not UNET_FP8:
+            raise ValueError("unet fp8: no layer is enabled by default (precision.UNET_FP8 is empty): name the layers with a pattern list")
+        return list(UNET_FP8)
+    if not isinstance(patterns, (list, tuple)) or not patterns or not all(isinstance(p, str) for p in patterns):
+        raise ValueError(f"unet fp8 is True or a list of layer-name patterns, got {patterns!r}")
+    return list(patterns)
+
+
+def set_fp8_unet_conv(model: nn.Module, patterns) -> int:
+    """Mark the convs of a UNet2DConditionModel whose names match `patterns` (a list of regular expressions, re.search; True = UNET_FP8) and
+    UNET_FP8_ELIGIBLE as fp8 (nn.Conv2d.fp8_deep); every other conv is unmarked. ValueError for anything else than True or a list of strings,
+    for a pattern that names no eligible layer (True included, should UNET_FP8 be empty), and outside the bf16 compute type. Returns how
+    many layers are marked."""
+    from . import ops
+    if ops.precise() or ops.act_dtype() != torch.bfloat16:
+        raise ValueError("fp8 UNet convolutions need the bf16 compute type (OMGSR-S's bf16 tier); the accurate tier and fp16 have none")
+    regs = [re.compile(p) for p in check_fp8_unet_conv(patterns)]
+    cand = _fp8_unet_candidates(model)
+    dead = [r.pattern for r in regs if not any(r.search(name) for name, _ in cand)]
+    if dead:            # a typo would otherwise run the plain bf16 tier without a word
+        raise ValueError(f"unet fp8 patterns that name no eligible layer (the resnet conv1 / conv2 of down_blocks / mid_block / up_blocks): {dead}")
+    _touch()
+    want = {name for name, _ in cand if any(r.search(name) for r in regs)}
+    n = 0
+    for name, m in model.named_modules():
+        if isinstance(m, Conv2d):
+            m.fp8_deep = name in want
+            n += m.fp8_deep
+    return n
+
+
+def clear_fp8_unet_conv(model: nn.Module) -> None:
+    """Unmark every fp8 UNet conv of `model` (a pipeline of another tier, or one without the key, built on marked modules)."""
+    if any(isinstance(m, Conv2d) and m.fp8_deep for m in model.modules()):
+        _touch()
+        for m in model.modules():
+            if isinstance(m, Conv2d):
+                m.fp8_deep = False
+
+
+def fp8_unet_conv_layers(model: nn.Module) -> list:
+    """Names of the fp8 UNet convs of `model`."""
+    return [name for name, m in model.named_modules() if isinstance(m, Conv2d) and m.fp8_deep]
+
+
+def refuse_fp8_unet_conv(policy, where: str) -> None:
+    """ValueError when a precision_policy asks for fp8 UNet convolutions anywhere but OMGSR-S's bf16 tier."""
+    if isinstance(policy, dict) and isinstance(policy.get("unet"), dict) and "fp8" in policy["unet"]:
+        raise ValueError(f"unet fp8 belongs to OMGSR-S's bf16 tier (weight_dtype=torch.bfloat16), not to {where}")
+
+
 def set_mx(model: nn.Module, patterns: Iterable[str]) -> int:
     """Move the both-sides split of the matching 3x3 stride-1 (halo-tile kernel) and 1x1 (MX GEMM kernel) convolutions (Cin % 64 == 0,
     >= 96 output channels) to the mixed-precision form (op_split 3); layers that do not qualify keep what they had. OMGSR_MX=0
