@@ -393,6 +393,27 @@ int omgsr_groupnorm_apply_mxfp8_c64(const void* x, void* codes, void* scales, co
 int omgsr_groupnorm_apply_mxfp8_multi(const omgsr_gn_apply_group* groups, int32_t ngroups, const float* mean, const float* rstd,
                                       const float* gamma, const float* beta, int32_t C, int32_t G, int32_t act, int32_t stat_rows,
                                       int32_t x_el, void* stream);
+/* Additive under ABI v22: the thin 3x3 stride-1 pad-1 convolutions at the edges of the networks as fp32 streaming kernels (conv_edge.hip): fp32
+ * FMAs in a fixed order on the fp32 stream tensor and the layer's UNSPLIT fp32 weights - no MFMA, no 16-bit operand, no saturation flag, no
+ * workspace. Group k of a launch is a tensor of `rows` maps of H x W pixels (the tile-shape groups of a tiled-VAE layer; one group otherwise).
+ *
+ * omgsr_conv_out_gn: y = conv3x3(silu((x - mean) rstd gamma + beta)) + bias for Cout <= 8 in ONE pass over x (replaces the GroupNorm apply pass
+ * and the conv behind it of conv_norm_out / conv_out). x f32 [rows][H][W][Cin] un-normalised, Cin % 32 == 0 up to 1024, Cin % G == 0; mean / rstd
+ * f32 [stat_rows][G], row r uses row r % stat_rows; gamma / beta f32 [Cin]; y f32 [rows][H][W][8] with channels >= Cout exact zeros.
+ * weight f32 [Cin / 4][3][3][4][CP]: element (q, ky, kx, e, co) is w[co][4 q + e][ky][kx]; CP = 4 for Cout <= 4, else 8,
+ * columns >= Cout zero. bias f32 [CP] or NULL. The normalised value is the one the apply kernels compute before their 16-bit rounding; the
+ * map is zero-padded AFTER the normalisation. H W Cin < 2^31. */
+typedef struct omgsr_edge_group {
+    const void* x;
+    void* y;
+    int32_t rows;
+    int32_t H;
+    int32_t W;
+    int32_t reserved;
+} omgsr_edge_group;
+int omgsr_conv_out_gn(const omgsr_edge_group* groups, int32_t ngroups, const float* mean, const float* rstd, const float* gamma,
+                      const float* beta, const float* weight, const float* bias, int32_t Cin, int32_t Cout, int32_t G, int32_t stat_rows,
+                      void* stream);
 int omgsr_groupnorm_finalize2(const float* partial_a, int32_t nslot_a, int32_t Ca, const float* partial_b, int32_t nslot_b, int32_t Cb,
                               float* mean, float* rstd, float* var_out, int32_t N, int32_t G, double count, float eps, void* stream);
 int omgsr_groupnorm_apply2(const void* xa, const void* xb, int32_t Ca, void* y, const float* mean, const float* rstd, const float* gamma,

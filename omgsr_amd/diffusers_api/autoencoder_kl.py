@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..nn import Conv2d, GroupNorm, Linear
+from ..nn import Conv2d, GroupNorm, Linear, norm_silu_conv
 from .modeling_utils import ConfigDict, ModelMixin
 
 SD21_VAE_CONFIG = dict(in_channels=3, out_channels=3, block_out_channels=[128, 256, 512, 512], layers_per_block=2,
@@ -320,7 +320,7 @@ class Encoder(nn.Module):
         for b in self.down_blocks:
             h = b.nhwc(h)
         h = self.mid_block.nhwc(h)
-        return self.conv_out.nhwc(h, gn=self.conv_norm_out.spec(h, ops.ACT_SILU))
+        return norm_silu_conv(self.conv_norm_out, self.conv_out, h)
 
     def run_nhwc(self, x):
         """nhwc() or, when a tiled-VAE hook is installed (pipelines.vaehook.VAEHook), the hook."""
@@ -355,7 +355,7 @@ class Decoder(nn.Module):
         h = self.mid_block.nhwc(h)
         for b in self.up_blocks:
             h = b.nhwc(h)
-        return self.conv_out.nhwc(h, gn=self.conv_norm_out.spec(h, ops.ACT_SILU))
+        return norm_silu_conv(self.conv_norm_out, self.conv_out, h)
 
     def run_nhwc(self, z):
         hook = getattr(self, "_tile_hook", None)

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..nn import Conv2d, GroupNorm, InputCache, LayerNorm, Linear, _key, bump_cache_epoch
+from ..nn import Conv2d, GroupNorm, InputCache, LayerNorm, Linear, _key, bump_cache_epoch, norm_silu_conv
 from .autoencoder_kl import Downsample2D, ResnetBlock2D, Upsample2D
 from .modeling_utils import ConfigDict, ModelMixin
 
@@ -326,7 +326,7 @@ class UNet2DConditionModel(ModelMixin):
                     h = blk.attentions[j].nhwc(h, ehs, out_for=last)
             if blk.upsamplers is not None:
                 h = blk.upsamplers[0].nhwc(h, gn_groups=g if ops.precise() else 0)        # accurate tier: the next norm1 folds these with its skip's
-        return self.conv_out.nhwc(h, gn=self.conv_norm_out.spec(h, ops.ACT_SILU))
+        return norm_silu_conv(self.conv_norm_out, self.conv_out, h)
 
     # ---- diffusers API ---------------------------------------------------------------------
     def forward(self, sample: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor, return_dict: bool = True):

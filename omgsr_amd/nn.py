@@ -188,6 +188,32 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
         self._pk8d, self._pk8d_key = None, None
         bump_cache_epoch()
 
+    # the accurate tiers' edge layers (csrc/conv_edge.hip): a conv_out behind its GroupNorm + SiLU on an fp32 stream tensor runs as ONE fp32
+    # kernel on the un-normalised map (ops.conv_out_gn_multi) instead of the apply pass + the MFMA conv. The call sites ask edge_out() and
+    # route; nhwc() / nhwc_multi() and the packs above do not change. The fp32 pack is lazy, under a key of its own like the MXFP8 forms
+    def edge_out(self, x: torch.Tensor, norm: "GroupNorm") -> bool:
+        return (self.groups == 1 and self.dilation == (1, 1) and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1]
+                and x.shape[-1] == self.in_channels
+                and ops.edge_conv_out_ok(x.dtype, self.weight.shape, self.stride[0], self.padding[0], norm.num_groups))
+
+    def packed_edge_out(self) -> "ops.EdgeWeight":
+        k = _key(self.weight, self.bias, "edge-out")
+        if getattr(self, "_pke_key", None) != k:
+            bump_cache_epoch()
+            _log_rebuild(self._drop_packed_edge_out)
+            self._pke = ops.pack_edge_out_weight(self.weight, self.bias)
+            self._pke_key = k
+        return self._pke
+
+    def _drop_packed_edge_out(self) -> None:
+        self._pke, self._pke_key = None, None
+        bump_cache_epoch()
+
+    def nhwc_edge_out_multi(self, xs, norm: "GroupNorm", mean: torch.Tensor, rstd: torch.Tensor):
+        """conv(silu(norm(x))) of every xs[k] with the statistics mean / rstd [nimg, G] (edge_out() said yes): [rows, H, W, Cout8] fp32."""
+        g, b = norm._affine()
+        return ops.conv_out_gn_multi(list(xs), self.packed_edge_out(), mean, rstd, g, b, norm.num_groups)
+
     def packed(self) -> ops.PackedWeight:
         # logical Cout widened to a multiple of 8 (zero rows): 3/4-channel heads write 16-byte NHWC rows
         sp, wsp, ph = self.in_split(), self.in_wsplit(), self.phase_upsample
@@ -302,6 +328,15 @@ class GroupNorm(nn.GroupNorm, _Packed):
         x4 = x.reshape(shp[0], shp[1], -1, 1) if x.dim() == 3 else x
         y = self.nhwc(ops.nchw_to_nhwc(x4.contiguous()))
         return ops.nhwc_to_nchw(y, dtype=ops.io_dtype(x)).to(x.dtype).reshape(shp)
+
+
+def norm_silu_conv(norm: GroupNorm, conv: Conv2d, h: torch.Tensor) -> torch.Tensor:
+    """conv(silu(norm(h))): the tail of the UNet and of the untiled VAE encoder / decoder (conv_norm_out, conv_out). Accurate tiers: the fp32
+    edge kernel; 16-bit tiers: the conv takes the norm as before."""
+    if conv.edge_out(h, norm):
+        mean, rstd, _ = norm.stats(h)
+        return conv.nhwc_edge_out_multi([h], norm, mean, rstd)[0]
+    return conv.nhwc(h, gn=norm.spec(h, ops.ACT_SILU))
 
 
 class LayerNorm(nn.LayerNorm, _Packed):

@@ -1774,6 +1774,70 @@ def group_norm_pair(a: torch.Tensor, b: torch.Tensor, gamma, beta, groups: int, 
 
 
 # --------------------------------------------------------------------------------------------
+# The thin 3x3 convolutions at the edges of the networks as fp32 streaming kernels (csrc/conv_edge.hip): the accurate tiers only
+# (fp32 stream tensors); the 16-bit tiers never come here. New wrappers the model code calls - conv2d / conv2d_multi are unchanged.
+
+@dataclass
+class EdgeWeight:
+    """A conv_out's fp32 weight as omgsr_conv_out_gn reads it: w [Cin / 4][3][3][4][CP] (CP = 4 | 8 columns), bias [CP]."""
+    w: torch.Tensor
+    bias: torch.Tensor
+    cin: int
+    cout: int
+
+
+def edge_conv_out_ok(stream: torch.dtype, weight_shape, stride: int, padding: int, groups: int) -> bool:
+    """The routing predicate of the call sites (VAEHook._run, Encoder / Decoder.nhwc, the UNet): a GroupNorm + SiLU + 3x3 stride-1 pad-1 conv
+    with at most 8 output channels on an fp32 stream tensor runs as omgsr_conv_out_gn; everything else (every 16-bit tier) as before."""
+    cout, cin, kh, kw = (int(v) for v in weight_shape)
+    return (stream == torch.float32 and (kh, kw) == (3, 3) and stride == 1 and padding == 1 and cout <= 8
+            and cin % 32 == 0 and cin <= 1024 and groups > 0 and cin % groups == 0)
+
+
+def pack_edge_out_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> EdgeWeight:
+    """[Cout, Cin, 3, 3] (any float dtype; used as fp32, unsplit and unrounded) -> EdgeWeight."""
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    if tuple(weight.shape[2:]) != (3, 3) or cout > 8 or cin % 4:
+        raise ValueError("pack_edge_out_weight: a 3x3 kernel, Cout <= 8, Cin % 4 == 0")
+    cp = 4 if cout <= 4 else 8
+    dev = device or weight.device
+    w = torch.zeros((cin // 4, 3, 3, 4, cp), device=dev, dtype=torch.float32)
+    w[..., :cout] = weight.detach().to(device=dev, dtype=torch.float32).reshape(cout, cin // 4, 4, 3, 3).permute(1, 3, 4, 2, 0)
+    b = torch.zeros((cp,), device=dev, dtype=torch.float32)
+    if bias is not None:
+        b[:cout] = bias.detach().to(device=dev, dtype=torch.float32)
+    return EdgeWeight(w.contiguous(), b, cin, cout)
+
+
+def conv_out_gn_multi(xs, ew: EdgeWeight, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int,
+                      one_launch: bool = True):
+    """conv3x3(silu(GroupNorm(x))) + bias of every xs[k] ([rows_k, h_k, w_k, Cin] fp32 stream tensors: the tile-shape groups of a tiled-VAE
+    layer) with the statistics mean / rstd [nimg, G] (row r of a tensor uses image r % nimg) -> list of [rows_k, h_k, w_k, 8] fp32, channels
+    beyond Cout exact zeros. One launch over a prefix table of the groups, or (one_launch False) one launch per tensor: the same bytes."""
+    if not 0 < len(xs) <= _lib.GN_MAX_GROUPS:
+        raise ValueError(f"1 ... {_lib.GN_MAX_GROUPS} tile shape groups")
+    for x in xs:
+        if _req(x, torch.float32, "x").dim() != 4 or x.shape[-1] != ew.cin:
+            raise ValueError(f"conv_out_gn: x must be [rows, H, W, {ew.cin}]")
+    outs = [torch.empty((*x.shape[:-1], 8), device=x.device, dtype=torch.float32) for x in xs]
+    desc = (_lib.EdgeGroup * len(xs))()
+    for k, x in enumerate(xs):
+        desc[k].x, desc[k].y = x.data_ptr(), outs[k].data_ptr()
+        desc[k].rows, desc[k].H, desc[k].W = x.shape[0], x.shape[1], x.shape[2]
+    fn = _lib.load().omgsr_conv_out_gn
+    for first, count in ([(0, len(xs))] if one_launch else [(k, 1) for k in range(len(xs))]):
+        check(fn(C.byref(desc[first]), count, _req(mean, torch.float32, "mean").data_ptr(), _req(rstd, torch.float32, "rstd").data_ptr(),
+                 _req(gamma, torch.float32, "gamma").data_ptr(), _req(beta, torch.float32, "beta").data_ptr(), ew.w.data_ptr(),
+                 ew.bias.data_ptr(), ew.cin, ew.cout, groups, mean.shape[0], _stream()), "omgsr_conv_out_gn")
+    return outs
+
+
+def conv_out_gn(x: torch.Tensor, ew: EdgeWeight, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                groups: int) -> torch.Tensor:
+    return conv_out_gn_multi([x], ew, mean, rstd, gamma, beta, groups)[0]
+
+
+# --------------------------------------------------------------------------------------------
 # K9/K10: LayerNorm (affine or AdaLN-modulated)
 
 def layer_norm(x: torch.Tensor, a: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float, split: int = 1) -> torch.Tensor:

@@ -134,6 +134,7 @@ class VAEHook:
         res: Dict[tuple, list] = {k: [] for k in groups}
         gi = 0
         pending = None          # a GroupNorm handed to the conv that follows it (ops.GnSpec): the conv's patch producer where the kernel can
+        edge = None             # (norm, mean, rstd) of a conv_norm_out whose conv_out runs as the fp32 edge kernel on the un-normalised tensors
         for op in seq:
             kind = op[0]
             if kind == "gn":
@@ -152,6 +153,10 @@ class VAEHook:
                 gi += 1
                 first = next(iter(groups.values()))
                 is_conv3 = getattr(op[3], "kernel_size", None) == (3, 3)
+                if op[3] is self.net.conv_out and act == ops.ACT_SILU and op[4] is None and op[3].edge_out(first, norm):
+                    # accurate tiers: conv_norm_out + SiLU + conv_out in one pass over the fp32 stream tensors, every shape group in ONE launch
+                    edge = (norm, mean, rstd)
+                    continue
                 if is_conv3 and first.dtype != torch.float32:
                     # a 16-bit stream tensor into a 3x3 conv: the conv takes the norm (fused into its patch producer, or applied in front of
                     # it: ops.conv2d_multi decides for the whole layer); the 1x1 shortcut reads the un-normalised tensor, which IS its operand
@@ -172,7 +177,12 @@ class VAEHook:
                         groups[k] = y
             elif kind == "conv":
                 keys = list(groups)
-                for k, y in zip(keys, op[1].nhwc_multi([groups[k] for k in keys], gn=pending, fp8=self.fp8_convs, **op[2])):
+                if edge is not None:
+                    outs = op[1].nhwc_edge_out_multi([groups[k] for k in keys], *edge)
+                    edge = None
+                else:
+                    outs = op[1].nhwc_multi([groups[k] for k in keys], gn=pending, fp8=self.fp8_convs, **op[2])
+                for k, y in zip(keys, outs):
                     groups[k] = y
                 pending = None
             elif kind == "res_push":
