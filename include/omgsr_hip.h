@@ -414,6 +414,30 @@ typedef struct omgsr_edge_group {
 int omgsr_conv_out_gn(const omgsr_edge_group* groups, int32_t ngroups, const float* mean, const float* rstd, const float* gamma,
                       const float* beta, const float* weight, const float* bias, int32_t Cin, int32_t Cout, int32_t G, int32_t stat_rows,
                       void* stream);
+/* Additive under ABI v22: norm1's apply pass of a ResnetBlock whose channel count changes, with the block's 1x1 conv_shortcut computed in the
+ * same pass over the fp32 stream tensor (norm_shortcut.hip; accurate tier, fp16 compute type). Replaces omgsr_groupnorm_apply_shared / _multi
+ * with a y2 twin plus the shortcut's omgsr_igemm: x is read once, no twin is written or re-read.
+ *   y  = act((x - mean) rstd gamma + beta) as an operand of kind y_el (OMGSR_EL_16 | OMGSR_EL_MX6): the bytes omgsr_groupnorm_apply_shared writes;
+ *   sc = x W^T + bias, f32 [rows][HW][N], from the un-normalised x: three fp16 MFMA segments x_hi w_hi + x_lo w_hi + x_hi w_lo in a fixed
+ *        order (the same bits from any grouping of the tensors into launches).
+ * x f32 [rows][HW][C]; mean / rstd f32 [stat_rows][G], row r uses row r % stat_rows; gamma / beta f32 [C] or NULL; bias f32 [N] or NULL.
+ * weight: fp16 [C / 64][4][N / 32][2][64][8] - element (chunk, step, tile, seg, lane, j) is the hi (seg 0) or lo (seg 1) half of
+ * w[32 tile + (lane & 31)][64 chunk + 16 step + 8 (lane >> 5) + j], hi = fp16(w), lo = fp16(w - hi).
+ * C, N in {128, 256, 512}, C % G == 0, act NONE | SILU: omgsr_groupnorm_shortcut_ok says whether a problem is served (1) under the current
+ * compute type; omgsr_groupnorm_shortcut returns OMGSR_E_SHAPE for anything else (never another kernel). overflow_flag (optional): ORed with 1
+ * when an x value lies beyond +-65504, as the twin-writing apply pass does. Group k of a launch is a tensor of `rows` x `HW` pixels. */
+typedef struct omgsr_gn_shortcut_group {
+    const void* x;
+    void* y;
+    void* sc;
+    int64_t HW;
+    int32_t rows;
+    int32_t reserved;
+} omgsr_gn_shortcut_group;
+int32_t omgsr_groupnorm_shortcut_ok(int32_t C, int32_t N, int32_t G, int32_t y_el);
+int omgsr_groupnorm_shortcut(const omgsr_gn_shortcut_group* groups, int32_t ngroups, const float* mean, const float* rstd,
+                             const float* gamma, const float* beta, const void* weight, const float* bias, int32_t C, int32_t N,
+                             int32_t G, int32_t act, int32_t stat_rows, int32_t y_el, uint32_t* overflow_flag, void* stream);
 int omgsr_groupnorm_finalize2(const float* partial_a, int32_t nslot_a, int32_t Ca, const float* partial_b, int32_t nslot_b, int32_t Cb,
                               float* mean, float* rstd, float* var_out, int32_t N, int32_t G, double count, float eps, void* stream);
 int omgsr_groupnorm_apply2(const void* xa, const void* xb, int32_t Ca, void* y, const float* mean, const float* rstd, const float* gamma,

@@ -63,6 +63,11 @@ class EdgeGroup(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("rows", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GnShortcutGroup(C.Structure):
+    """One tensor of an omgsr_groupnorm_shortcut launch (omgsr_gn_shortcut_group)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("sc", C.c_void_p), ("HW", C.c_int64), ("rows", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [
         ("q", C.c_void_p), ("k", C.c_void_p), ("vt", C.c_void_p), ("o", C.c_void_p),
@@ -125,6 +130,8 @@ SIGNATURES = {
     "omgsr_groupnorm_apply_shared": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "omgsr_groupnorm_apply_multi": (C.c_int, [C.POINTER(GnApplyGroup), _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "omgsr_conv_out_gn": (C.c_int, [C.POINTER(EdgeGroup), _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "omgsr_groupnorm_shortcut_ok": (C.c_int32, [_I, _I, _I, _I]),
+    "omgsr_groupnorm_shortcut": (C.c_int, [C.POINTER(GnShortcutGroup), _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "omgsr_groupnorm_finalize2": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, C.c_double, _F, _P]),
     "omgsr_groupnorm_apply2": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _I, _P, _P]),
     "omgsr_image_to_model_input": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),

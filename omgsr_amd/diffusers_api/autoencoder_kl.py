@@ -57,6 +57,11 @@ class ResnetBlock2D(nn.Module):
             # (apply -> conv1's operand, twin -> the shortcut's): it is not built where both producers left per-channel statistics
             h, xc = self.norm1.nhwc_pair(x[0], x[1], ops.ACT_SILU, split=self.conv1.in_split(), also_cast=self.conv_shortcut.in_split())
             h = self.conv1.nhwc(h, bias_override=conv1_bias, gn_groups=self.norm2.num_groups)
+        elif self.conv_shortcut is not None and x.dtype == torch.float32 and self.conv_shortcut.gn_shortcut(x, self.norm1, self.conv1.in_split()):
+            # accurate tier, fp16 operands: the 1x1 shortcut is computed inside norm1's apply pass over x (no operand copy of x at all)
+            h, sc = self.norm1.nhwc_shortcut(x, self.conv_shortcut, ops.ACT_SILU, split=self.conv1.in_split())
+            h = self.conv1.nhwc(h, bias_override=conv1_bias, gn_groups=self.norm2.num_groups)
+            xc = None
         elif self.conv_shortcut is not None and x.dtype == torch.float32:
             # accurate tier: the 1x1 shortcut reads x itself; its operand copy is a second output of norm1's apply pass over x
             h, xc = self.norm1.nhwc(x, ops.ACT_SILU, split=self.conv1.in_split(), also_cast=self.conv_shortcut.in_split())
@@ -65,7 +70,8 @@ class ResnetBlock2D(nn.Module):
             xc = x
             h = self.conv1.nhwc(x, gn=self.norm1.spec(x, ops.ACT_SILU), bias_override=conv1_bias, gn_groups=self.norm2.num_groups)   # norm2's statistics ride the epilogue
         g2 = self.norm2.spec(h, ops.ACT_SILU)
-        sc = self.conv_shortcut.nhwc(xc, pad=0) if self.conv_shortcut is not None else x
+        if xc is not None:
+            sc = self.conv_shortcut.nhwc(xc, pad=0) if self.conv_shortcut is not None else x
         if out_for is not None:
             return self.conv2.nhwc(h, gn=g2, residual=sc, out_dtype=ops.OUT_BF16, out_split=out_for.in_split())
         return self.conv2.nhwc(h, gn=g2, residual=sc, gn_groups=self.norm1.num_groups)      # ... and the next block's norm1

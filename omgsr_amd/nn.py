@@ -214,6 +214,28 @@ class Conv2d(nn.Conv2d, _Packed, _Operand):
         g, b = norm._affine()
         return ops.conv_out_gn_multi(list(xs), self.packed_edge_out(), mean, rstd, g, b, norm.num_groups)
 
+    # the accurate tier's channel-changing ResnetBlocks (csrc/norm_shortcut.hip): this 1x1 conv_shortcut is computed inside norm1's apply pass
+    # over the fp32 stream tensor (ops.group_norm_shortcut*) instead of as a GEMM on a cast twin of it. The call sites ask gn_shortcut() and
+    # route; nhwc() and the packs above do not change. The hi / lo fp16 pack is lazy, under a key of its own like the other forms
+    def gn_shortcut(self, x: torch.Tensor, norm: "GroupNorm", split: int) -> bool:
+        """split: the operand form norm1's consumer (conv1) asked for."""
+        return (self.groups == 1 and self.dilation == (1, 1) and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1]
+                and x.shape[-1] == self.in_channels == norm.num_channels and not self.out_inner16
+                and ops.gn_shortcut_ok(x.dtype, self.weight.shape, self.stride[0], self.padding[0], norm.num_groups, split))
+
+    def packed_gn_shortcut(self) -> "ops.ShortcutWeight":
+        k = _key(self.weight, self.bias, "gn-shortcut")
+        if getattr(self, "_pks_key", None) != k:
+            bump_cache_epoch()
+            _log_rebuild(self._drop_packed_gn_shortcut)
+            self._pks = ops.pack_gn_shortcut_weight(self.weight, self.bias)
+            self._pks_key = k
+        return self._pks
+
+    def _drop_packed_gn_shortcut(self) -> None:
+        self._pks, self._pks_key = None, None
+        bump_cache_epoch()
+
     def packed(self) -> ops.PackedWeight:
         # logical Cout widened to a multiple of 8 (zero rows): 3/4-channel heads write 16-byte NHWC rows
         sp, wsp, ph = self.in_split(), self.in_wsplit(), self.phase_upsample
@@ -322,6 +344,18 @@ class GroupNorm(nn.GroupNorm, _Packed):
         """apply_stats over the tile-shape groups of a tiled-VAE layer in one launch (the same bytes as one call per group)."""
         g, b = self._affine()
         return ops.group_norm_apply_multi(xs, mean, rstd, g, b, self.num_groups, act, split=split, also_cast=also_cast)
+
+    def nhwc_shortcut(self, x, shortcut: "Conv2d", act=ops.ACT_NONE, split=1):
+        """nhwc(x, act, split) and the 1x1 `shortcut` of the un-normalised x from ONE pass over x (shortcut.gn_shortcut() said yes):
+        (operand, fp32 shortcut result)."""
+        g, b = self._affine()
+        mean, rstd, _ = ops.group_norm_stats(x, self.num_groups, self.eps)
+        return ops.group_norm_shortcut(x, shortcut.packed_gn_shortcut(), mean, rstd, g, b, self.num_groups, act, split)
+
+    def apply_stats_shortcut_multi(self, xs, mean, rstd, shortcut: "Conv2d", act=ops.ACT_NONE, split=1):
+        """The same over the tile-shape groups of a tiled-VAE layer with supplied statistics, in one launch: [(operand, shortcut result)]."""
+        g, b = self._affine()
+        return ops.group_norm_shortcut_multi(list(xs), shortcut.packed_gn_shortcut(), mean, rstd, g, b, self.num_groups, act, split)
 
     def forward(self, x):  # NCHW (or [B, C, L]) compat
         shp = x.shape

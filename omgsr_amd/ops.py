@@ -1838,6 +1838,95 @@ def conv_out_gn(x: torch.Tensor, ew: EdgeWeight, mean: torch.Tensor, rstd: torch
 
 
 # --------------------------------------------------------------------------------------------
+# norm1's apply pass with the block's 1x1 conv_shortcut computed in it (csrc/norm_shortcut.hip): the accurate tier with fp16 operands only.
+# New wrappers the model code calls - group_norm* with also_cast, to_operand and conv2d are unchanged and serve everything else.
+
+GN_SHORTCUT_CHANNELS = (128, 256, 512)
+GN_SHORTCUT_SPLITS = (1, 4)          # y forms: plain fp16, OMGSR_EL_MX6
+
+
+@dataclass
+class ShortcutWeight:
+    """A 1x1 conv_shortcut's weight as omgsr_groupnorm_shortcut streams it: w fp16 [Cin / 64][4][Cout / 32][hi | lo][64 lanes][8]
+    (include/omgsr_hip.h), bias fp32 [Cout]."""
+    w: torch.Tensor
+    bias: torch.Tensor
+    cin: int
+    cout: int
+
+
+def gn_shortcut_enabled() -> bool:
+    """OMGSR_GN_SHORTCUT_FUSED=0 restores the apply-with-twin + shortcut GEMM path (A/B runs)."""
+    return os.environ.get("OMGSR_GN_SHORTCUT_FUSED", "1") != "0"
+
+
+def gn_shortcut_ok(stream: torch.dtype, weight_shape, stride: int, padding: int, groups: int, split: int) -> bool:
+    """The routing predicate of the call sites (ResnetBlock2D.nhwc, VAEHook._run): a GroupNorm apply whose result is a plain fp16 or MX6
+    operand (split 1 | 4), on an fp32 stream tensor under fp16 operands, next to a 1x1 stride-1 unpadded shortcut with Cin and Cout in
+    {128, 256, 512} runs as omgsr_groupnorm_shortcut; everything else (every 16-bit tier, the bf16-operand range-fallback tier, other operand
+    forms and channel counts, the switch off) as before."""
+    if len(weight_shape) != 4:
+        return False
+    cout, cin, kh, kw = (int(v) for v in weight_shape)
+    return (gn_shortcut_enabled() and _PRECISE and _ACT == torch.float16 and stream == torch.float32 and (kh, kw) == (1, 1) and stride == 1
+            and padding == 0 and cin in GN_SHORTCUT_CHANNELS and cout in GN_SHORTCUT_CHANNELS and groups > 0 and cin % groups == 0
+            and split in GN_SHORTCUT_SPLITS)
+
+
+def pack_gn_shortcut_weight(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> ShortcutWeight:
+    """[Cout, Cin, 1, 1] (any float dtype; taken as fp32) -> ShortcutWeight: hi = fp16(w), lo = fp16(w - hi), both in the kernel's
+    B-fragment order (lane l of a 16-channel step holds column l & 31, channels 8 (l >> 5) ... + 7)."""
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    if tuple(weight.shape[2:]) != (1, 1) or cin % 64 or cout % 32:
+        raise ValueError("pack_gn_shortcut_weight: a 1x1 kernel, Cin % 64 == 0, Cout % 32 == 0")
+    dev = device or weight.device
+    w = _note_weight_range(weight.detach().to(device=dev, dtype=torch.float32).reshape(cout, cin))
+    hi = w.to(torch.float16)
+    lo = (w - hi.float()).to(torch.float16)
+
+    def frag(m):        # [Cout, Cin] -> [chunk][step][column tile][lane half][column][8]
+        return m.reshape(cout // 32, 32, cin // 64, 4, 2, 8).permute(2, 3, 0, 4, 1, 5)
+
+    pk = torch.stack((frag(hi), frag(lo)), dim=3).contiguous().reshape(cin // 64, 4, cout // 32, 2, 64, 8)
+    b = torch.zeros((cout,), device=dev, dtype=torch.float32)
+    if bias is not None:
+        b.copy_(bias.detach().to(device=dev, dtype=torch.float32))
+    return ShortcutWeight(pk, b, cin, cout)
+
+
+def group_norm_shortcut_multi(xs, sw: ShortcutWeight, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int, act: int = ACT_NONE,
+                              split: int = 1, one_launch: bool = True):
+    """For every xs[k] ([rows_k, ..., Cin] fp32 stream tensors: the tile-shape groups of a tiled-VAE layer, or one tensor) the pair
+    (y, sc): y = act(GroupNorm(x)) as the operand `split` names (the bytes of group_norm_apply_shared), sc = the 1x1 shortcut of the
+    un-normalised x, fp32 [rows_k, ..., Cout]. mean / rstd [nimg, G]: row r uses image r % nimg. One launch over a prefix table of the
+    groups, or (one_launch False) one launch per tensor: the same bytes."""
+    if not 0 < len(xs) <= _lib.GN_MAX_GROUPS:
+        raise ValueError(f"1 ... {_lib.GN_MAX_GROUPS} tile shape groups")
+    if split not in GN_SHORTCUT_SPLITS:
+        raise ValueError("group_norm_shortcut: y is a plain (split 1) or MX6 (split 4) operand")
+    for x in xs:
+        if _req(x, torch.float32, "x").shape[-1] != sw.cin:
+            raise ValueError(f"group_norm_shortcut: x must be [rows, ..., {sw.cin}]")
+    ys = [_operand_like(x, split) for x in xs]
+    scs = [torch.empty((*x.shape[:-1], sw.cout), device=x.device, dtype=torch.float32) for x in xs]
+    desc = (_lib.GnShortcutGroup * len(xs))()
+    for k, x in enumerate(xs):
+        desc[k].x, desc[k].y, desc[k].sc = x.data_ptr(), ys[k].data_ptr(), scs[k].data_ptr()
+        desc[k].rows, desc[k].HW = x.shape[0], x.numel() // (x.shape[0] * sw.cin)
+    fn = _lib.load().omgsr_groupnorm_shortcut
+    for first, count in ([(0, len(xs))] if one_launch else [(k, 1) for k in range(len(xs))]):
+        check(fn(C.byref(desc[first]), count, _req(mean, torch.float32, "mean").data_ptr(), _req(rstd, torch.float32, "rstd").data_ptr(),
+                 _ptr(gamma), _ptr(beta), sw.w.data_ptr(), sw.bias.data_ptr(), sw.cin, sw.cout, groups, act, mean.shape[0],
+                 _el_of_split(split), _ovf(xs[0].device), _stream()), "omgsr_groupnorm_shortcut")
+    return list(zip(ys, scs))
+
+
+def group_norm_shortcut(x: torch.Tensor, sw: ShortcutWeight, mean: torch.Tensor, rstd: torch.Tensor, gamma, beta, groups: int,
+                        act: int = ACT_NONE, split: int = 1):
+    return group_norm_shortcut_multi([x], sw, mean, rstd, gamma, beta, groups, act, split)[0]
+
+
+# --------------------------------------------------------------------------------------------
 # K9/K10: LayerNorm (affine or AdaLN-modulated)
 
 def layer_norm(x: torch.Tensor, a: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float, split: int = 1) -> torch.Tensor:

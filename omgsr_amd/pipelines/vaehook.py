@@ -167,7 +167,13 @@ class VAEHook:
                     continue
                 # rows (tile, image) share the image's statistics; every shape group in ONE apply launch, like the convs around it
                 keys = list(groups)
-                if op[4] is not None:
+                if op[4] is not None and op[4].gn_shortcut(first, norm, op[3].in_split()):
+                    # accurate tier, fp16 operands: the shortcut is computed inside the apply pass (csrc/norm_shortcut.hip), every shape group in ONE launch
+                    outs = norm.apply_stats_shortcut_multi([groups[k] for k in keys], mean, rstd, op[4], act, split=op[3].in_split())
+                    for k, (y, sc) in zip(keys, outs):
+                        groups[k] = y
+                        res[k].append(sc)
+                elif op[4] is not None:
                     outs = norm.apply_stats_multi([groups[k] for k in keys], mean, rstd, act, split=op[3].in_split(), also_cast=op[4].in_split())
                     for k, (y, xc) in zip(keys, outs):
                         groups[k] = y
