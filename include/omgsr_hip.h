@@ -196,6 +196,23 @@ typedef struct omgsr_igemm_args {
  * a->out 16-byte aligned. Residual, gate, GroupNorm statistics, out_lo_off, LAYOUT_T and a problem that is not mxf8 return OMGSR_E_SHAPE
  * (never another kernel). Rows >= M and columns >= Cout are not written. Timing: kind OMGSR_TK_IGEMM, variant 18. */
 int omgsr_igemm_out_mxfp8(const omgsr_igemm_args* a, void* out_scale, int64_t out_scale_ld, void* stream);
+/* Additive under ABI v22 (new entry points; no struct changes): the GEGLU form of the MXFP8 token GEMM, mxfp8_gemm_geglu_kernel - a
+ * feed-forward's first projection, out = (x Wa^T + bias_a) * gelu(x Wg^T + bias_g) with the exact (erf) GELU. `weight` / `w_scale` hold
+ * pack_geglu_weight's interleave, [32 a | 32 gate] per 64 PACKED rows, as OMGSR_EL_MXFP8 planes of Cout_pad rows (rows past 2 Cout: zero
+ * codes, zero scale bytes); `bias` is f32 [Cout_pad] in the same interleave (or NULL). Cout counts the logical columns (inner), Cout_pad the
+ * packed rows. Served: mxf8 = 1, act OMGSR_ACT_GEGLU, GEMM-shaped (1x1, stride 1, no padding / upsampling, in_ld 0), Cin % 128 == 0,
+ * K_pad == Cin, Cout_pad % 256 == 0, Cout % 32 == 0, 2 Cout <= Cout_pad, batch 1, NHWC, bf16 compute type, alpha 1, no residual, gate,
+ * GroupNorm statistics, split fields, out_mx, out_lo_off or LAYOUT_T, out_ld % 8 == 0, a->out 16-byte aligned. A K that is no multiple of
+ * 128 (the UNet's C = 320) is served by padding: operand and weight carry K rounded up to 128, the pad holding what the quantiser makes of
+ * zero channels - codes 0x00 under scale byte 0x00 (omgsr_layernorm_mxfp8_pad writes it, the packer pads the weight).
+ * out_scale NULL: a plain [M][out_ld] output, bf16 or fp32 per out_dtype. out_scale given: the OMGSR_EL_MXFP8 form under
+ * omgsr_igemm_out_mxfp8's rules (codes to a->out with out_ld % 16 == 0, scale bytes to out_scale [M][out_scale_ld], 0 = Cout / 32,
+ * out_dtype OMGSR_OUT_BF16) - exactly the bytes omgsr_quantize_mxfp8 makes of the bf16 output of the same call. Rows >= M and columns >= Cout
+ * are not written. Anything else returns OMGSR_E_SHAPE and launches nothing (never another kernel); omgsr_igemm and omgsr_igemm_out_mxfp8
+ * keep refusing OMGSR_ACT_GEGLU for an mxf8 problem. omgsr_igemm_geglu_mxfp8_ok: 1 when the block is one the plain form serves.
+ * Timing: kind OMGSR_TK_IGEMM, variant 28. */
+int32_t omgsr_igemm_geglu_mxfp8_ok(const omgsr_igemm_args* a);
+int omgsr_igemm_geglu_mxfp8(const omgsr_igemm_args* a, void* out_scale, int64_t out_scale_ld, void* stream);
 /* Additive under ABI v22 (no struct changed): `count` independent mxf8 problems through mxfp8_gemm_multi_kernel, at most 4 per launch (a
  * larger `count` runs as successive launches of at most 4, in the order given; a group of one launches mxfp8_gemm_kernel, variant 18). Each
  * problem keeps its own M, K, N, tensors, weight, bias, act, gate, residual, output kind (bf16 / fp32 / OMGSR_LAYOUT_T), out_ld and strides;
@@ -465,6 +482,13 @@ int omgsr_quantize_mxfp8_ld(const void* x, int32_t x_el, int64_t rows, int32_t K
  * c_ld % 8 == 0, `codes` 8-byte aligned, s_ld >= C / 32; anything else (fp32 input, fp16 compute type) returns OMGSR_E_SHAPE. Timing kind OMGSR_TK_LN. */
 int omgsr_layernorm_mxfp8(const void* x, const float* a, const float* b, int64_t rows, int32_t C, float eps, int32_t x_el, void* codes,
                           void* scales, int64_t c_ld, int64_t s_ld, void* stream);
+/* Additive under ABI v22: omgsr_layernorm_mxfp8 for rows whose consumer carries K padded to a multiple of 128 (omgsr_igemm_geglu_mxfp8 at the
+ * UNet's C = 320). C % 32 == 0, C <= 4096; both pitches are required: c_ld >= roundup128(C), c_ld % 8 == 0, s_ld >= roundup128(C) / 32,
+ * `codes` 8-byte aligned. Columns [0, C) get omgsr_layernorm_mxfp8's bytes ("omgsr_layernorm writes bf16, omgsr_quantize_mxfp8 reads it");
+ * code columns [C, roundup128(C)) and their scale bytes get 0x00 - what the quantiser makes of zero channels; nothing past roundup128(C) is
+ * touched. For C % 128 == 0 the bytes are omgsr_layernorm_mxfp8's. fp32 input and the fp16 compute type return OMGSR_E_SHAPE. */
+int omgsr_layernorm_mxfp8_pad(const void* x, const float* a, const float* b, int64_t rows, int32_t C, float eps, int32_t x_el, void* codes,
+                              void* scales, int64_t c_ld, int64_t s_ld, void* stream);
 /* Stream tensor -> MFMA operand: y = x rounded to the compute type (y_el OMGSR_EL_16) or its two-term split
  * (OMGSR_EL_SPLIT); x f32 [rows][C], C % 8 == 0. (Inputs of convs that no norm precedes: up / down-sampling convs,
  * 1x1 shortcuts, conv_in, proj_out, post_quant_conv.) */
@@ -658,7 +682,8 @@ int omgsr_timing_reset(void);
  * 18 mxfp8_gemm_kernel (ABI v18), 21 mxfp8_conv_kernel (ABI v22), 22 mxfp8_conv_multi_kernel (several problems of one layer in one launch),
  * 24 mxfp8_gemm_multi_kernel (up to 4 independent MXFP8 GEMMs in one launch: omgsr_igemm_mxfp8_multi), 25 mxfp8_conv_up_kernel (nearest-2x
  * up-sampling + 3x3 conv in MXFP8, phase-decomposed), 26 mxfp8_conv_up_multi_kernel (several problems of one layer in one launch),
- * 27 mxfp8_conv_deep_kernel (the MXFP8 3x3 conv with staged operand scales: Cin % 64 == 0 up to 2048).
+ * 27 mxfp8_conv_deep_kernel (the MXFP8 3x3 conv with staged operand scales: Cin % 64 == 0 up to 2048), 28 mxfp8_gemm_geglu_kernel (the GEGLU
+ * form of the MXFP8 token GEMM: omgsr_igemm_geglu_mxfp8).
  * variant (attention): 0 attn_kernel, 19 mxfp8_attn_kernel (ABI v19), 20 vae_attn_kernel (ABI v20, D = 512), 23 vae_attn_full_kernel (D = 512, every operand a two-term split). flops / bytes: ALGORITHMIC work of the launch (a two-term split operand's duplicated
  * channels count once). */
 typedef struct omgsr_timing_entry { int32_t kind; float ms; double flops; double bytes; int64_t m, n, k; int32_t variant; int32_t stage; } omgsr_timing_entry;

@@ -99,6 +99,8 @@ SIGNATURES = {
     "omgsr_error_string": (C.c_char_p, [C.c_int]),
     "omgsr_igemm": (C.c_int, [C.POINTER(IgemmArgs), _P]),
     "omgsr_igemm_out_mxfp8": (C.c_int, [C.POINTER(IgemmArgs), _P, _L, _P]),
+    "omgsr_igemm_geglu_mxfp8_ok": (C.c_int32, [C.POINTER(IgemmArgs)]),
+    "omgsr_igemm_geglu_mxfp8": (C.c_int, [C.POINTER(IgemmArgs), _P, _L, _P]),
     "omgsr_igemm_mxfp8_multi_ok": (C.c_int32, [C.POINTER(IgemmArgs), _I]),
     "omgsr_igemm_mxfp8_multi": (C.c_int, [C.POINTER(IgemmArgs), _I, _P]),
     "omgsr_igemm_multi_plan": (C.c_int, [C.POINTER(IgemmArgs), _I]),
@@ -147,6 +149,7 @@ SIGNATURES = {
     "omgsr_quantize_mxfp8": (C.c_int, [_P, _I, _L, _I, _L, _P, _P, _P]),
     "omgsr_quantize_mxfp8_ld": (C.c_int, [_P, _I, _L, _I, _L, _P, _P, _L, _L, _P]),
     "omgsr_layernorm_mxfp8": (C.c_int, [_P, _P, _P, _L, _I, _F, _I, _P, _P, _L, _L, _P]),
+    "omgsr_layernorm_mxfp8_pad": (C.c_int, [_P, _P, _P, _L, _I, _F, _I, _P, _P, _L, _L, _P]),
     "omgsr_attention": (C.c_int, [C.POINTER(AttnArgs), _P]),
     "omgsr_softmax_rows": (C.c_int, [_P, _P, _L, _I, _I, _P]),
     "omgsr_softmax_rows_split": (C.c_int, [_P, _P, _L, _I, _I, _P]),

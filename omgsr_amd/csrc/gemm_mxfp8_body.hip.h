@@ -1,6 +1,7 @@
 // Body of mxfp8_gemm_kernel (gemm_mxfp8.hip describes the schedule), shared by its two instantiations: the 16-bit / fp32 output forms
 // (gemm_mxfp8.hip) and OUT8, whose epilogue writes the OMGSR_EL_MXFP8 form (gemm_mxfp8_out8.hip: a translation unit of its own, like
 // igemm_halo_out6.hip - see igemm_epilogue.hip.h at OUT6 for why an output form is a template flag and not a run-time branch).
+// mxfp8_gemm_geglu_kernel (gemm_mxfp8_geglu.hip) instantiates both once more over pack_geglu_weight's interleaved rows, act OMGSR_ACT_GEGLU.
 #pragma once
 #include "common.hip.h"
 #include "../../include/omgsr_hip.h"

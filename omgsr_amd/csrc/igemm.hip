@@ -899,6 +899,36 @@ extern "C" int omgsr_igemm_out_mxfp8(const omgsr_igemm_args* ap, void* out_scale
     return omgsr::mxfp8_gemm_out8_launch(a, g, (unsigned char*)out_scale, out_scale_ld > 0 ? out_scale_ld : a.Cout / 32, st);
 }
 
+// Additive under ABI v22: the GEGLU form of the MXFP8 token GEMM (a feed-forward's first projection over pack_geglu_weight's interleaved rows) -
+// mxfp8_gemm_geglu_kernel or nothing. out_scale NULL: the plain [M][Cout] output; otherwise the OMGSR_EL_MXFP8 form under omgsr_igemm_out_mxfp8's
+// pitch and alignment rules. omgsr_igemm and omgsr_igemm_out_mxfp8 keep refusing GEGLU.
+namespace {
+bool igemm_geglu_mxfp8_ok(const omgsr_igemm_args& a, const bool out8, const int64_t out_scale_ld) {
+    if (!a.in || !a.weight || !a.out || !omgsr::mxfp8_gemm_geglu_ok(a) || ((uintptr_t)a.out & 15)) return false;
+    if (out8 && (a.out_dtype != OMGSR_OUT_BF16 || (a.out_ld & 15) || out_scale_ld < 0 || (out_scale_ld > 0 && out_scale_ld < a.Cout / 32))) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int32_t omgsr_igemm_geglu_mxfp8_ok(const omgsr_igemm_args* ap) { return (ap && igemm_geglu_mxfp8_ok(*ap, false, 0)) ? 1 : 0; }
+
+extern "C" int omgsr_igemm_geglu_mxfp8(const omgsr_igemm_args* ap, void* out_scale, int64_t out_scale_ld, void* stream) {
+    if (!ap) return OMGSR_E_BADARG;
+    const omgsr_igemm_args& a = *ap;
+    if (!igemm_geglu_mxfp8_ok(a, out_scale != nullptr, out_scale_ld)) return OMGSR_E_SHAPE;
+    const int64_t M64 = (int64_t)a.N * a.Ho * a.Wo;
+    Geo g{};
+    g.M = (int)M64;
+    g.HoWo = a.Ho * a.Wo;
+    g.Hv = a.H;
+    g.Wv = a.W;
+    g.nk = a.K_pad / BK;
+    hipStream_t st = (hipStream_t)stream;
+    double flops, bytes;
+    work_of(a, &flops, &bytes, out_scale != nullptr);
+    return omgsr::mxfp8_gemm_geglu_launch(a, g, (unsigned char*)out_scale, out_scale_ld > 0 ? out_scale_ld : a.Cout / 32, st, flops, bytes);     // (timing variant 28)
+}
+
 // ---- additive under ABI v22: up to 4 independent MXFP8 token GEMMs per launch through mxfp8_gemm_multi_kernel ----------------------------
 namespace {
 constexpr int MXG_MULTI_MAX = 4;                // problems per launch (gemm_mxfp8_multi.hip)

@@ -17,6 +17,8 @@ bool mxfp8_gemm_ok(const omgsr_igemm_args& a);                                 /
 int mxfp8_gemm_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st);
 int mxfp8_gemm_out8_launch(const omgsr_igemm_args& a, IgemmGeo g, unsigned char* out_scale, int64_t out_scale_ld, hipStream_t st);   // gemm_mxfp8_out8.hip
 int mxfp8_gemm_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int count, hipStream_t st, double flops, double bytes);   // gemm_mxfp8_multi.hip
+bool mxfp8_gemm_geglu_ok(const omgsr_igemm_args& a);                           // gemm_mxfp8_geglu.hip: the GEGLU form (out_scale NULL: the plain output)
+int mxfp8_gemm_geglu_launch(const omgsr_igemm_args& a, IgemmGeo g, unsigned char* out_scale, int64_t out_scale_ld, hipStream_t st, double flops, double bytes);
 bool mxfp8_conv_shape_ok(const omgsr_igemm_args& a);                                                            // conv_mxfp8.hip
 int mxfp8_conv_launch(const omgsr_igemm_args& a, IgemmGeo g, hipStream_t st, double flops);
 int mxfp8_conv_launch_multi(const omgsr_igemm_args* a, const IgemmGeo* g0, int count, hipStream_t st, double flops);

@@ -411,16 +411,31 @@ OMGSR_DEVINL void load_affine8(const float* __restrict__ v, const int c, const f
 // YEL = OMGSR_EL_MXFP8 (omgsr_layernorm_mxfp8, additive under ABI v22): y is the code plane and `mx` carries the scale plane and the two pitches; the result
 // is rounded to bf16 as the 16-bit store rounds it and quantised in registers (mxfp8_quad_octet: C % 128 == 0 keeps every lane quad of
 // octets lane + 64 i all-live or all-dead). Every other form takes the empty LnPlain and compiles as before.
+// YEL = LN_MXFP8_PAD (omgsr_layernorm_mxfp8_pad, additive under ABI v22; instantiations of their own, the ones above compile as before): the MXFP8 form
+// for C % 32 == 0 (a lane quad of octets is still all-live or all-dead) whose rows carry K padded to a multiple of 128 - the octets
+// [C / 8, roundup128(C) / 8) of a row get zero codes and zero scale bytes, what the quantiser makes of zero channels (ln_pad8_mxfp8).
 struct LnMx8 { unsigned char* scales; int64_t c_ld, s_ld; };
 struct LnPlain {};
-template <int YEL> using ln_extra_t = typename std::conditional<YEL == OMGSR_EL_MXFP8, LnMx8, LnPlain>::type;
+constexpr int LN_MXFP8_PAD = 105;               // internal: not an element kind of the ABI
+template <int YEL> constexpr bool ln_is_mxfp8 = YEL == OMGSR_EL_MXFP8 || YEL == LN_MXFP8_PAD;
+template <int YEL> using ln_extra_t = typename std::conditional<ln_is_mxfp8<YEL>, LnMx8, LnPlain>::type;
 template <int YEL>
 OMGSR_DEVINL void ln_store8_mxfp8(void* y, const ln_extra_t<YEL>& mx, const int64_t row, const int c8, const float (&o8)[8]) {
-    if constexpr (YEL == OMGSR_EL_MXFP8) {
+    if constexpr (ln_is_mxfp8<YEL>) {
         int s;
         const u32x2_t out = mxfp8_quad_octet(o8, s);
         *reinterpret_cast<u32x2_t*>(reinterpret_cast<unsigned char*>(y) + row * mx.c_ld + c8 * 8) = out;
         if ((c8 & 3) == 0) mx.scales[row * mx.s_ld + (c8 >> 2)] = (unsigned char)s;
+    }
+}
+// the pad octet c8 of a row (nch8 <= c8 < nch8 rounded up to 16): inside the planes' pitches by omgsr_layernorm_mxfp8_pad's checks
+template <int YEL>
+OMGSR_DEVINL void ln_pad8_mxfp8(void* y, const ln_extra_t<YEL>& mx, const int64_t row, const int c8, const int nch8) {
+    if constexpr (YEL == LN_MXFP8_PAD) {
+        if (c8 >= nch8 && c8 < ((nch8 + 15) & ~15)) {
+            *reinterpret_cast<u32x2_t*>(reinterpret_cast<unsigned char*>(y) + row * mx.c_ld + c8 * 8) = (u32x2_t){0u, 0u};
+            if ((c8 & 3) == 0) mx.scales[row * mx.s_ld + (c8 >> 2)] = (unsigned char)0;
+        }
     }
 }
 
@@ -496,11 +511,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
                     o8[e] = (f[r][i][e] - mu[r]) * rs * (PRE ? av[PRE ? i : 0][e] : ga[e]) + (PRE ? bv[PRE ? i : 0][e] : be[e]);
-                if constexpr (YEL == OMGSR_EL_MXFP8) ln_store8_mxfp8<YEL>(y, mx, row0 + r, c8, o8);
+                if constexpr (ln_is_mxfp8<YEL>) ln_store8_mxfp8<YEL>(y, mx, row0 + r, c8, o8);
                 else if constexpr (YEL == 3) {
                     if constexpr (std::is_same<T, f16_t>::value) store8_mx<T>(y, (row0 + r) * 4 * (int64_t)C, C, c8 * 8, o8);   // OMGSR_EL_MX row: 4C bytes
                 } else store8<T, YEL>(y, (row0 + r) * (YEL == 2 ? 2 * C : C) + c8 * 8, C, o8);
-            }
+            } else ln_pad8_mxfp8<YEL>(y, mx, row0 + r, c8, nch8);       // (64 MAXCH octets cover the padded row: 64 MAXCH is a multiple of 16)
         }
     }
 }
@@ -550,11 +565,11 @@ __global__ __launch_bounds__(256) void layernorm_block_kernel(const void* __rest
             load_affine8(a, c8 * 8, 1.0f, ga); load_affine8(b, c8 * 8, 0.0f, be);
 #pragma unroll
             for (int e = 0; e < 8; ++e) o8[e] = (f[i][e] - mu) * rs * ga[e] + be[e];
-            if constexpr (YEL == OMGSR_EL_MXFP8) ln_store8_mxfp8<YEL>(y, mx, row, c8, o8);       // (octets t + 256 i: quads as in layernorm_kernel)
+            if constexpr (ln_is_mxfp8<YEL>) ln_store8_mxfp8<YEL>(y, mx, row, c8, o8);       // (octets t + 256 i: quads as in layernorm_kernel)
             else if constexpr (YEL == 3) {
                 if constexpr (std::is_same<T, f16_t>::value) store8_mx<T>(y, row * 4 * (int64_t)C, C, c8 * 8, o8);
             } else store8<T, YEL>(y, row * (YEL == 2 ? 2 * C : C) + c8 * 8, C, o8);
-        }
+        } else ln_pad8_mxfp8<YEL>(y, mx, row, c8, nch8);
     }
 }
 
@@ -1202,7 +1217,7 @@ int layernorm_launch(const void* x, void* y, const float* a, const float* b, int
                      const ln_extra_t<YEL> mx = ln_extra_t<YEL>{}) {
     const int nch = ((C >> 3) + 63) / 64;
     // (the MXFP8 form exists for the bf16 compute type only: no fp16 instantiation)
-#define LN_GO(...) do { if constexpr (YEL == OMGSR_EL_MXFP8) { using T = bf16_t; __VA_ARGS__; } else OMGSR_DISPATCH_T(__VA_ARGS__); } while (0)
+#define LN_GO(...) do { if constexpr (ln_is_mxfp8<YEL>) { using T = bf16_t; __VA_ARGS__; } else OMGSR_DISPATCH_T(__VA_ARGS__); } while (0)
     auto grid = [&](int rpw) { return dim3((unsigned)((rows + 4 * rpw - 1) / (4 * rpw))); };
     if (nch <= 1) LN_GO(hipLaunchKernelGGL((layernorm_kernel<T, 1, 4, XF32, YEL>), grid(4), dim3(256), 0, st, x, y, a, b, rows, C, eps, mx));
     else if (nch <= 2) LN_GO(hipLaunchKernelGGL((layernorm_kernel<T, 2, 4, XF32, YEL>), grid(4), dim3(256), 0, st, x, y, a, b, rows, C, eps, mx));
@@ -1238,6 +1253,19 @@ extern "C" int omgsr_layernorm_mxfp8(const void* x, const float* a, const float*
     hipStream_t st = (hipStream_t)stream;
     omgsr::TimingScope ts(OMGSR_TK_LN, 0.0, (2.0 + 1.0 + 1.0 / 32.0) * (double)rows * C, st);
     return layernorm_launch<false, OMGSR_EL_MXFP8>(x, codes, a, b, rows, C, eps, st, LnMx8{(unsigned char*)scales, c_ld, s_ld});
+}
+
+// Additive under ABI v22: omgsr_layernorm_mxfp8 for C % 32 == 0 with the rows' K padded to a multiple of 128 (zero codes, zero scale bytes) - the
+// operand of omgsr_igemm_geglu_mxfp8 at the UNet's C = 320. The pitches are required and cover the padded row.
+extern "C" int omgsr_layernorm_mxfp8_pad(const void* x, const float* a, const float* b, int64_t rows, int32_t C, float eps, int32_t x_el, void* codes,
+                                         void* scales, int64_t c_ld, int64_t s_ld, void* stream) {
+    if (!x || !codes || !scales || rows <= 0 || C <= 0) return OMGSR_E_BADARG;
+    const int64_t Cp = ((int64_t)C + 127) / 128 * 128;
+    if (x_el != OMGSR_EL_16 || omgsr::compute_dtype() != 0 || (C % 32) || C > 4096 || c_ld < Cp || (c_ld & 7) || s_ld < Cp / 32 ||
+        ((uintptr_t)codes & 7)) return OMGSR_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    omgsr::TimingScope ts(OMGSR_TK_LN, 0.0, (2.0 * C + (1.0 + 1.0 / 32.0) * (double)Cp) * (double)rows, st);
+    return layernorm_launch<false, LN_MXFP8_PAD>(x, codes, a, b, rows, C, eps, st, LnMx8{(unsigned char*)scales, c_ld, s_ld});
 }
 
 extern "C" int omgsr_softmax_rows(const float* s, void* p, int64_t rows, int32_t L, int32_t Lvalid, void* stream) {

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..nn import Conv2d, GroupNorm, InputCache, LayerNorm, Linear, _key, bump_cache_epoch, norm_silu_conv
+from ..nn import Conv2d, GroupNorm, InputCache, LayerNorm, Linear, _key, _log_rebuild, bump_cache_epoch, norm_silu_conv
 from .autoencoder_kl import Downsample2D, ResnetBlock2D, Upsample2D
 from .modeling_utils import ConfigDict, ModelMixin
 
@@ -142,18 +142,50 @@ class GEGLU(nn.Module):
             self._pk, self._pk_key = ops.pack_geglu_weight(self.proj.weight, self.proj.bias, split=sp, w_split=wsp), k
         return self._pk
 
+    # OMGSR-S's bf16 tier (precision.set_fp8_unet_ff): this projection runs as mxfp8_gemm_geglu_kernel on the MXFP8 LayerNorm output where the
+    # routing rule admits the problem (FeedForward.fp8_routed). The bf16 pack above stays; the MXFP8 form is packed lazily next to it, under a
+    # key of its own that names the form, and a rebuild under graph capture is logged
+    fp8 = False
+
+    def packed_mxfp8(self) -> ops.PackedWeight:
+        k = _key(self.proj.weight, self.proj.bias, "mxfp8-geglu")
+        if getattr(self, "_pk8_key", None) != k:
+            bump_cache_epoch()
+            _log_rebuild(self._drop_packed_mxfp8)
+            self._pk8 = ops.pack_geglu_weight_mxfp8(self.proj.weight, self.proj.bias)
+            self._pk8_key = k
+        return self._pk8
+
+    def _drop_packed_mxfp8(self) -> None:
+        self._pk8, self._pk8_key = None, None
+        bump_cache_epoch()
+
 
 class FeedForward(nn.Module):
     def __init__(self, dim: int, mult: int = 4):
         super().__init__()
         self.net = nn.ModuleList([GEGLU(dim, dim * mult), nn.Dropout(0.0), Linear(dim * mult, dim)])
 
+    def fp8_routed(self, rows: int) -> bool:
+        """Whether this feed-forward takes the MXFP8 chain for a problem of `rows` tokens: marked (precision.set_fp8_unet_ff), under the bf16
+        tier, and admitted by the one routing rule (precision.fp8_unet_ff_routed)."""
+        if not (self.net[0].fp8 and self.net[2].fp8) or ops.precise() or ops.act_dtype() != torch.bfloat16:
+            return False
+        from ..precision import fp8_unet_ff_routed
+        return fp8_unet_ff_routed(rows, self.net[0].proj.in_features)
+
     def nhwc(self, xn, residual, out_for=None):
+        if isinstance(xn, ops.Mxfp8):  # (BasicTransformerBlock asked fp8_routed): GEGLU GEMM -> MXFP8 hidden -> net.2 + the bf16 residual
+            h = ops.linear(xn, self.net[0].packed_mxfp8(), out_mxfp8=True)
+            if out_for is not None:
+                return self.net[2].nhwc(h, residual=residual, out_dtype=ops.OUT_BF16, out_split=out_for.in_split())
+            return self.net[2].nhwc(h, residual=residual)
+        net2 = self.net[2].packed_plain() if self.net[2].fp8 else self.net[2].packed()    # a marked block on a problem the rule refuses: today's path
         # a * gelu(gate) in the GEMM epilogue; the hidden tensor is the operand of net[2]
         h = ops.linear(xn, self.net[0].packed(), out_dtype=ops.OUT_BF16, out_split=self.net[2].in_split())
         if out_for is not None:       # the sum's only consumer is that linear (Transformer2DModel.proj_out): write its operand directly
-            return self.net[2].nhwc(h, residual=residual, out_dtype=ops.OUT_BF16, out_split=out_for.in_split())
-        return self.net[2].nhwc(h, residual=residual)
+            return ops.linear(h, net2, residual=residual, out_dtype=ops.OUT_BF16, out_split=out_for.in_split())
+        return ops.linear(h, net2, residual=residual)
 
 
 class BasicTransformerBlock(nn.Module):
@@ -169,6 +201,9 @@ class BasicTransformerBlock(nn.Module):
     def nhwc(self, y, ehs, out_for=None):
         y = self.attn1.self_nhwc(self.norm1.nhwc(y, split=self.attn1.in_split()), y)
         y = self.attn2.cross_nhwc(self.norm2.nhwc(y, split=self.attn2.in_split()), ehs, y)
+        if self.ff.fp8_routed(y.numel() // y.shape[-1]):       # norm3 writes the GEGLU GEMM's MXFP8 operand, K padded to 128 (C = 320 -> 384)
+            a, b = self.norm3._affine()
+            return self.ff.nhwc(ops.layer_norm_mxfp8(y, a, b, self.norm3.eps, pad128=True), y, out_for=out_for)
         return self.ff.nhwc(self.norm3.nhwc(y, split=self.ff.net[0].proj.in_split()), y, out_for=out_for)
 
 

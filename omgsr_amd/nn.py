@@ -294,6 +294,22 @@ class Linear(nn.Linear, _Packed, _Operand):
         sp, wsp = self.in_split(), self.in_wsplit()
         return self._packed(lambda: ops.pack_linear_weight(self.weight, self.bias, split=sp, w_split=wsp), self.weight, self.bias, sp, wsp)
 
+    def packed_plain(self) -> ops.PackedWeight:
+        """The 16-bit pack of an fp8-marked layer, for the problems its caller keeps off the MXFP8 path (the UNet's routed feed-forwards,
+        precision.fp8_unet_ff_routed): packed() without the mark, in a slot of its own so that the two forms do not evict each other."""
+        sp, wsp = self.in_split(), self.in_wsplit()
+        k = _key(self.weight, self.bias, sp, wsp, "plain")
+        if getattr(self, "_pkp_key", None) != k:
+            bump_cache_epoch()
+            _log_rebuild(self._drop_packed_plain)
+            self._pkp = ops.pack_linear_weight(self.weight, self.bias, split=sp, w_split=wsp)
+            self._pkp_key = k
+        return self._pkp
+
+    def _drop_packed_plain(self) -> None:
+        self._pkp, self._pkp_key = None, None
+        bump_cache_epoch()
+
     def nhwc(self, x, *, act=ops.ACT_NONE, residual=None, gate=None, out_dtype=ops.OUT_STREAM, gn_groups=0, out_split=1, out_mxfp8=None):
         """out_mxfp8 (an fp8 layer only; True or an Mxfp8 to write into): the result as an Mxfp8, from the GEMM's epilogue (ops.linear)."""
         return ops.linear(x, self.packed(), act=act, residual=residual, gate=gate, out_dtype=out_dtype, gn_groups=gn_groups,

@@ -656,6 +656,31 @@ def pack_linear_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor],
     return PackedWeight(q.codes, b, cout, cin, 1, 1, w_scale=q.scales)
 
 
+def pack_geglu_weight_mxfp8(weight: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> PackedWeight:
+    """GEGLU projection [2 * inner, in] bf16 -> the weight of omgsr_igemm_geglu_mxfp8: rows interleaved as pack_geglu_weight does
+    ([32 a | 32 gate] per 64 packed rows), K zero-padded to a multiple of 128 (the UNet's C = 320 -> 384: the operand carries the same pad,
+    layer_norm_mxfp8(pad128=True)) and the packed rows to a multiple of 256, quantised on the device (quantize_mxfp8: a zero block is codes
+    0x00 under scale byte 0x00). `cout` = inner, `cin` = the padded K; the bias is interleaved the same way, fp32, zero-padded to the rows."""
+    if _PRECISE or _ACT != torch.bfloat16:
+        raise ValueError("an fp8 (MXFP8) layer needs the bf16 compute type; the accurate tier and fp16 have none")
+    dev = device or weight.device
+    two_inner, cin = weight.shape
+    inner = two_inner // 2
+    if two_inner % 2 or inner % 32:
+        raise ValueError("GEGLU inner dim must be a multiple of 32")
+    kp, rows = _round_up(cin, 128), _round_up(two_inner, 256)
+    wd = weight.detach().to(device=dev, dtype=torch.bfloat16)
+    w = torch.zeros((rows, kp), device=dev, dtype=torch.bfloat16)
+    w[:two_inner, :cin] = torch.stack([wd[:inner].reshape(inner // 32, 32, cin), wd[inner:].reshape(inner // 32, 32, cin)], dim=1).reshape(two_inner, cin)
+    q = quantize_mxfp8(w)
+    b = None
+    if bias is not None:
+        bd = bias.detach().to(device=dev, dtype=torch.float32)
+        b = torch.zeros(rows, device=dev, dtype=torch.float32)
+        b[:two_inner] = torch.stack([bd[:inner].reshape(-1, 32), bd[inner:].reshape(-1, 32)], dim=1).reshape(two_inner)
+    return PackedWeight(q.codes, b, inner, kp, 1, 1, geglu=True, w_scale=q.scales)
+
+
 def _fp8_operand(x, pw: PackedWeight, what: str) -> Optional[Mxfp8]:
     """The MXFP8 operand of an fp8 weight (a bf16 tensor is quantised here); None for the other weight forms, which take no MXFP8 operand."""
     if not pw.fp8:
@@ -828,6 +853,40 @@ def _fill_out_mxfp8(a: IgemmArgs, dst: Mxfp8, row0: int, col0: int) -> tuple:
 def _igemm_out_mxfp8(a: IgemmArgs, scale: tuple, what: str) -> None:
     """Launch omgsr_igemm_out_mxfp8 (never splits K: no workspace)."""
     check(_lib.load().omgsr_igemm_out_mxfp8(C.byref(a), scale[0], scale[1], _stream()), what)
+
+
+def _fill_geglu_mxfp8(a: IgemmArgs, xq: Mxfp8, pw: PackedWeight, M: int) -> None:
+    """The argument block of omgsr_igemm_geglu_mxfp8 but for its output: an MXFP8 operand [M, K] against pack_geglu_weight_mxfp8's weight (the
+    operand's K is the pack's padded K); `Cout` counts the logical columns, `Cout_pad` the packed rows."""
+    _fill_mxfp8(a, xq.codes.data_ptr(), xq.scales.data_ptr(), pw)
+    _fill_gemm(a, M)
+    a.act, a.alpha, a.sample_rows = ACT_GEGLU, 1.0, M
+
+
+def _igemm_geglu_mxfp8(a: IgemmArgs, scale: Optional[tuple], what: str) -> None:
+    """Launch omgsr_igemm_geglu_mxfp8: scale = (scale pointer, scale pitch) of the OMGSR_EL_MXFP8 output (_fill_out_mxfp8), None = the plain output."""
+    check(_lib.load().omgsr_igemm_geglu_mxfp8(C.byref(a), scale[0] if scale else None, scale[1] if scale else 0, _stream()), what)
+
+
+def _linear_geglu_mxfp8(xq: Mxfp8, pw: PackedWeight, out_dtype: int, dst8: Optional[Mxfp8]):
+    """linear() of an MXFP8 operand against an fp8 GEGLU pack: mxfp8_gemm_geglu_kernel. dst8: the hidden tensor as an Mxfp8 - from the GEMM's
+    epilogue, or (FP8_FUSED_QUANT["gemm"] off: the pass form) from quantize_mxfp8 over the bf16 output; the same bytes."""
+    lead = xq.codes.shape[:-1]
+    M = xq.codes.numel() // pw.cin
+    a = IgemmArgs()
+    _fill_geglu_mxfp8(a, xq, pw, M)
+    if dst8 is not None and FP8_FUSED_QUANT["gemm"]:
+        scale = _fill_out_mxfp8(a, dst8.reshape(M, -1), 0, 0)
+        _igemm_geglu_mxfp8(a, scale, "omgsr_igemm_geglu_mxfp8(linear, out_mxfp8)")
+        return dst8
+    out = _out_tensor(lead, pw.cout, OUT_BF16 if dst8 is not None else out_dtype, 1, xq.codes.device)
+    _fill_out(a, out, 1, None, pw.cout)
+    _igemm_geglu_mxfp8(a, None, "omgsr_igemm_geglu_mxfp8(linear)")
+    if dst8 is None:
+        return out
+    if dst8.codes.shape[-1] == pw.cout:
+        return quantize_mxfp8(out, out=dst8)
+    return quantize_mxfp8(out, out=dst8, out_col=0)
 
 
 def _out_mxfp8_dst(what: str, out_mxfp8, pw: PackedWeight, lead, device, col0: int = 0, *, residual=None, gate=None, plain: bool = True) -> Optional[Mxfp8]:
@@ -1267,7 +1326,8 @@ def linear(x: torch.Tensor, pw: PackedWeight, *, act: int = ACT_NONE, residual: 
            out_split: int = 1, out_mxfp8=None):
     """x [..., K] -> [..., Cout]. gn_groups > 0 (x [B, ..., K]): the result feeds a GroupNorm over each x[b]; the GEMM
     then runs as B images of prod(...) rows so its epilogue can leave the per-image statistics (see conv2d).
-    An fp8-packed weight (pack_linear_weight_mxfp8) takes an Mxfp8 operand, or quantises a bf16 `x` first.
+    An fp8-packed weight (pack_linear_weight_mxfp8) takes an Mxfp8 operand, or quantises a bf16 `x` first. An fp8 GEGLU pack
+    (pack_geglu_weight_mxfp8; the operand carries the pack's padded K) runs mxfp8_gemm_geglu_kernel: bias only, plain or out_mxfp8 output.
     out_mxfp8 (fp8-packed weight only; True or a dense Mxfp8 [..., Cout] to write into): the result act(x W^T + bias) as an Mxfp8 - the bytes
     of quantize_mxfp8(linear(..., out_dtype=OUT_BF16)), written by the GEMM's epilogue. No residual, gate, statistics or split."""
     if out_mxfp8 is not None and out_mxfp8 is not False:
@@ -1280,6 +1340,10 @@ def linear(x: torch.Tensor, pw: PackedWeight, *, act: int = ACT_NONE, residual: 
     if xq is not None:
         if gn_groups or out_split != 1:
             raise ValueError("linear: an fp8 layer writes a plain output (no GroupNorm statistics, no split)")
+        if pw.geglu:                                # pack_geglu_weight_mxfp8: the GEGLU form of the kernel, its own entry point
+            if act != ACT_NONE or residual is not None or gate is not None or alpha != 1.0:
+                raise ValueError("linear: an fp8 GEGLU projection goes with its bias only (no act, residual, gate or alpha)")
+            return _linear_geglu_mxfp8(xq, pw, out_dtype, dst8)
         lead = xq.codes.shape[:-1]
         M = xq.codes.numel() // pw.cin
         a = IgemmArgs()
@@ -1940,13 +2004,35 @@ def layer_norm(x: torch.Tensor, a: Optional[torch.Tensor], b: Optional[torch.Ten
     return y
 
 
-def layer_norm_mxfp8(x: torch.Tensor, a: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float, out: Optional[Mxfp8] = None) -> Mxfp8:
+def layer_norm_mxfp8(x: torch.Tensor, a: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float, out: Optional[Mxfp8] = None,
+                     pad128: bool = False) -> Mxfp8:
     """bf16 stream tensor rows [..., C] (the fp8 tier; C % 128 == 0, C <= 4096) -> the normalised rows as an Mxfp8, written by the LayerNorm
-    kernel itself (omgsr_layernorm_mxfp8): the bytes of quantize_mxfp8(layer_norm(x, a, b, eps)). out: a dense Mxfp8 of x's shape."""
+    kernel itself (omgsr_layernorm_mxfp8): the bytes of quantize_mxfp8(layer_norm(x, a, b, eps)). out: a dense Mxfp8 of x's shape.
+    pad128 (C % 32 == 0; no `out`): the Mxfp8's last dim is C rounded up to 128, the pad holding zero codes under zero scale bytes - the operand
+    of a GEMM whose weight carries the same K pad (pack_geglu_weight_mxfp8). omgsr_layernorm_mxfp8_pad, or with FP8_FUSED_QUANT["layernorm"] off
+    the pass form (bf16 layer_norm, zero-pad, quantize_mxfp8): the same bytes."""
     if x.dtype != torch.bfloat16 or _ACT != torch.bfloat16 or _PRECISE:
         raise ValueError("layer_norm_mxfp8: a bf16 stream tensor under the bf16 compute type (the fp8 tier)")
     _req(x, torch.bfloat16, "x")
     Cc = x.shape[-1]
+    if pad128:
+        if out is not None:
+            raise ValueError("layer_norm_mxfp8: pad128 allocates its result")
+        if Cc % 32 or Cc > 4096:
+            raise ValueError(f"layer_norm_mxfp8: C = {Cc} must be a multiple of 32, at most 4096")
+        Kp = _round_up(Cc, 128)
+        if not FP8_FUSED_QUANT["layernorm"]:
+            y = layer_norm(x, a, b, eps)
+            if Kp != Cc:
+                yp = torch.zeros((*x.shape[:-1], Kp), device=x.device, dtype=torch.bfloat16)
+                yp[..., :Cc] = y
+                y = yp
+            return quantize_mxfp8(y)
+        out = Mxfp8(torch.empty((*x.shape[:-1], Kp), device=x.device, dtype=torch.uint8),
+                    torch.empty((*x.shape[:-1], Kp // 32), device=x.device, dtype=torch.uint8))
+        check(_lib.load().omgsr_layernorm_mxfp8_pad(x.data_ptr(), _ptr(a), _ptr(b), x.numel() // Cc, Cc, eps, EL_16, out.codes.data_ptr(),
+                                                    out.scales.data_ptr(), Kp, Kp // 32, _stream()), "omgsr_layernorm_mxfp8_pad")
+        return out
     if Cc % 128 or Cc > 4096:
         raise ValueError(f"layer_norm_mxfp8: C = {Cc} must be a multiple of 128, at most 4096")
     if out is None:

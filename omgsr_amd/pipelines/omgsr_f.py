@@ -60,8 +60,9 @@ class OMGSR_F_Infer(torch.nn.Module):
             raise ValueError("the fp8 tier's precision_policy is {'flux': {'fp8': [patterns], 'fp8_attention': True | [block patterns]}, "
                              "'vae': {'fp8': True | [layer patterns], 'fp8_upsample': True | [layer patterns]}}")
         if not fp8:
-            from ..precision import refuse_fp8_attention, refuse_fp8_conv, refuse_fp8_unet_conv, refuse_fp8_upsample
+            from ..precision import refuse_fp8_attention, refuse_fp8_conv, refuse_fp8_unet_conv, refuse_fp8_unet_ff, refuse_fp8_upsample
             refuse_fp8_unet_conv(precision_policy, "OMGSR-F")           # (the fp8 tier refuses the "unet" key above)
+            refuse_fp8_unet_ff(precision_policy, "OMGSR-F")
             refuse_fp8_attention(precision_policy, f"the {weight_dtype} tier")
             refuse_fp8_conv(precision_policy, f"the {weight_dtype} tier")
             refuse_fp8_upsample(precision_policy, f"the {weight_dtype} tier")

@@ -39,20 +39,28 @@ class OMGSR_S_Infer(torch.nn.Module):
         refuse_fp8_upsample(precision_policy, "OMGSR-S")
         # precision_policy={"unet": {"fp8": True | [layer patterns]}} (bf16 tier only, opt-in): those resnet convs of the UNet run as MXFP8
         # convolutions where the deep-K kernel serves them (precision.set_fp8_unet_conv); checked before anything is loaded
-        from ..precision import check_fp8_unet_conv, refuse_fp8_unet_conv
-        fp8_unet = None
+        # {"unet": {"fp8_ff": True | [block patterns]}} (bf16 tier only, opt-in, beside or without "fp8"): those transformer blocks' feed-forwards
+        # run norm3 -> MXFP8 -> GEGLU GEMM -> MXFP8 hidden -> net.2 in MXFP8 (precision.set_fp8_unet_ff)
+        from ..precision import check_fp8_unet_conv, check_fp8_unet_ff, refuse_fp8_unet_conv, refuse_fp8_unet_ff
+        fp8_unet = fp8_ff = None
         if isinstance(precision_policy, dict) and "unet" in precision_policy:
             u = precision_policy["unet"]
-            if not isinstance(u, dict) or not set(u) <= {"fp8", "act", "weight", "inner16"}:
-                raise ValueError("OMGSR-S's precision_policy['unet'] is {'fp8': True | [layer patterns]} on the bf16 tier, "
-                                 "{'act': [...], 'weight': [...], 'inner16': [...]} on the accurate tier")
+            if not isinstance(u, dict) or not set(u) <= {"fp8", "fp8_ff", "act", "weight", "inner16"}:
+                raise ValueError("OMGSR-S's precision_policy['unet'] is {'fp8': True | [layer patterns], 'fp8_ff': True | [block patterns]} on the "
+                                 "bf16 tier, {'act': [...], 'weight': [...], 'inner16': [...]} on the accurate tier")
             if weight_dtype != torch.bfloat16:
                 refuse_fp8_unet_conv(precision_policy, f"the {weight_dtype} tier")
+                refuse_fp8_unet_ff(precision_policy, f"the {weight_dtype} tier")
             fp8_unet = u.get("fp8")
             if fp8_unet is False:
                 fp8_unet = None
             if fp8_unet is not None:
                 check_fp8_unet_conv(fp8_unet)
+            fp8_ff = u.get("fp8_ff")
+            if fp8_ff is False:
+                fp8_ff = None
+            if fp8_ff is not None:
+                check_fp8_unet_ff(fp8_ff)
         # --weight_dtype picks the tier: bf16 / fp16 = that 16-bit type end to end; fp32 = the accurate tier (fp32 stream
         # tensors, fp16 MFMA operands, two-term split operands where the precision policy says so)
         ops.set_compute_dtype(weight_dtype)
@@ -72,12 +80,17 @@ class OMGSR_S_Infer(torch.nn.Module):
         self.vae = vae.to(device=device, dtype=weight_dtype).eval()
         self.unet = unet.to(device=device, dtype=weight_dtype).eval()
         self.device = device
-        from ..precision import RangeFallback, clear_fp8_unet_conv, set_fp8_unet_conv
+        from ..precision import RangeFallback, clear_fp8_unet_conv, clear_fp8_unet_ff, set_fp8_unet_conv, set_fp8_unet_ff
         if fp8_unet is not None:
             set_fp8_unet_conv(self.unet, fp8_unet)
         else:
             clear_fp8_unet_conv(self.unet)
         self.fp8_unet = fp8_unet is not None
+        if fp8_ff is not None:
+            set_fp8_unet_ff(self.unet, fp8_ff)
+        else:
+            clear_fp8_unet_ff(self.unet)
+        self.fp8_unet_ff = fp8_ff is not None
         if weight_dtype == torch.float32:       # which layers carry two-term split operands / weights (omgsr_amd/precision.py)
             from ..precision import resolve
             resolve(precision_policy, vae=self.vae, unet=self.unet)

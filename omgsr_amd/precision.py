@@ -512,6 +512,103 @@ def refuse_fp8_unet_conv(policy, where: str) -> None:
         raise ValueError(f"unet fp8 belongs to OMGSR-S's bf16 tier (weight_dtype=torch.bfloat16), not to {where}")
 
 
+# The UNet's feed-forwards on OMGSR-S's bf16 tier (opt-in: precision_policy={"unet": {"fp8_ff": True | [block patterns]}}, beside or without the
+# "fp8" key, weight_dtype=bfloat16 only): a marked BasicTransformerBlock runs norm3 -> MXFP8 (ops.layer_norm_mxfp8, K padded to 128 at
+# C = 320) -> mxfp8_gemm_geglu_kernel -> MXFP8 hidden -> net.2 on mxfp8_gemm_kernel + the bf16 residual, wherever fp8_unet_ff_routed admits the
+# problem; every other problem of a marked block takes the bf16 path bit for bit. A pattern names transformer BLOCKS
+# (`...attentions.J.transformer_blocks.0`); UNET_FP8_FF_ELIGIBLE is the hard limit - all sixteen of SD 2.1's - and UNET_FP8_FF is what `True`
+# marks: every eligible block - which of a marked block's problems move is the routing rule's business, and the quality table of DESIGN.md 3.6
+# was measured with that list under that rule: 37.9-40.8 dB against the accurate tier on three seeded draws (target >= 30 dB). Beside
+# {"fp8": True} draw 0 falls to 29.55 dB; beside "fp8" narrowed to the 32-wide level or to the up path all three draws hold 35.0 dB or more.
+UNET_FP8_FF_ELIGIBLE = [r"\.attentions\.\d+\.transformer_blocks\.\d+$"]
+UNET_FP8_FF = list(UNET_FP8_FF_ELIGIBLE)
+# the smallest measured (rows, C) class of each width that won: profiles/fp8_unet_ff.json
+FF_ROUTED_MIN_C, FF_ROUTED_MIN_WORK = 640, 2304 * 1280
+
+
+def fp8_unet_ff_served(rows: int, C: int) -> bool:
+    """Every shape the library serves: C % 32 == 0 (the LayerNorm producer; the GEGLU GEMM's inner = 4 C is then a multiple of 32 and net.2's
+    K = 4 C a multiple of 128), C <= 4096."""
+    return rows > 0 and C % 32 == 0 and 32 <= C <= 4096
+
+
+def fp8_unet_ff_routed(rows: int, C: int) -> bool:
+    """THE routing rule of a marked feed-forward: whether a problem of `rows` tokens and width C takes the MXFP8 chain. Its content is the
+    measurement of tools/bench_fp8_unet_ff.py (profiles/fp8_unet_ff.json): a shape class is admitted only if every MXFP8 step
+    of it was faster than every bf16 step of it. Admitted: (36864, 640), (9216, 640), (9216, 1280), (2304, 1280) - C >= 640 with
+    rows x C >= 2304 x 1280. Excluded: every class at C = 320 ((147456, 320) wins 1.08x at the median but one of its nine MXFP8 steps was
+    slower than the fastest bf16 step; (36864, 320) and (4096, 320) lose), and the small problems (576, 1280), (1024, 640), (256, 1280),
+    (64, 1280), which lose 0.57-0.80x: one or two 256-row tiles do not fill the device. Sizes between the measured classes count as excluded."""
+    return fp8_unet_ff_served(rows, C) and C >= FF_ROUTED_MIN_C and rows * C >= FF_ROUTED_MIN_WORK
+
+
+def _fp8_unet_ff_candidates(model: nn.Module):
+    from .diffusers_api.unet_2d_condition import BasicTransformerBlock
+    elig = [re.compile(p) for p in UNET_FP8_FF_ELIGIBLE]
+    return [(name, m) for name, m in model.named_modules() if isinstance(m, BasicTransformerBlock) and any(r.search(name) for r in elig)]
+
+
+def check_fp8_unet_ff(patterns) -> list:
+    """The model-independent half of set_fp8_unet_ff: True -> UNET_FP8_FF (ValueError should it be empty), a non-empty list of strings ->
+    itself, ValueError for anything else."""
+    if patterns is True:
+        if not UNET_FP8_FF:
+            raise ValueError("unet fp8_ff: no block is enabled by default (precision.UNET_FP8_FF is empty): name the blocks with a pattern list")
+        return list(UNET_FP8_FF)
+    if not isinstance(patterns, (list, tuple)) or not patterns or not all(isinstance(p, str) for p in patterns):
+        raise ValueError(f"unet fp8_ff is True or a list of block-name patterns, got {patterns!r}")
+    return list(patterns)
+
+
+def _mark_fp8_ff(block, on: bool) -> None:
+    block.ff.net[0].fp8 = on
+    block.ff.net[2].fp8 = on
+
+
+def set_fp8_unet_ff(model: nn.Module, patterns) -> int:
+    """Mark the feed-forwards of the transformer blocks of a UNet2DConditionModel whose names match `patterns` (regular expressions, re.search;
+    True = UNET_FP8_FF) and UNET_FP8_FF_ELIGIBLE: GEGLU.fp8 and net.2's Linear.fp8; every other block is unmarked. ValueError for anything else
+    than True or a list of strings, for a pattern that names no eligible block, and outside the bf16 compute type. Returns how many blocks
+    are marked."""
+    from . import ops
+    if ops.precise() or ops.act_dtype() != torch.bfloat16:
+        raise ValueError("fp8 UNet feed-forwards need the bf16 compute type (OMGSR-S's bf16 tier); the accurate tier and fp16 have none")
+    regs = [re.compile(p) for p in check_fp8_unet_ff(patterns)]
+    cand = _fp8_unet_ff_candidates(model)
+    dead = [r.pattern for r in regs if not any(r.search(name) for name, _ in cand)]
+    if dead:            # a typo would otherwise run the plain bf16 tier without a word
+        raise ValueError(f"unet fp8_ff patterns that name no eligible block (attentions.J.transformer_blocks.K): {dead}")
+    _touch()
+    n = 0
+    for name, m in cand:
+        on = any(r.search(name) for r in regs)
+        _mark_fp8_ff(m, on)
+        n += on
+    return n
+
+
+def clear_fp8_unet_ff(model: nn.Module) -> None:
+    """Unmark every fp8 feed-forward of `model` (a pipeline of another tier, or one without the key, built on marked modules)."""
+    from .diffusers_api.unet_2d_condition import BasicTransformerBlock
+    blocks = [m for m in model.modules() if isinstance(m, BasicTransformerBlock)]
+    if any(m.ff.net[0].fp8 or m.ff.net[2].fp8 for m in blocks):
+        _touch()
+        for m in blocks:
+            _mark_fp8_ff(m, False)
+
+
+def fp8_unet_ff_layers(model: nn.Module) -> list:
+    """Names of the transformer blocks of `model` whose feed-forward is marked fp8."""
+    from .diffusers_api.unet_2d_condition import BasicTransformerBlock
+    return [name for name, m in model.named_modules() if isinstance(m, BasicTransformerBlock) and m.ff.net[0].fp8]
+
+
+def refuse_fp8_unet_ff(policy, where: str) -> None:
+    """ValueError when a precision_policy asks for fp8 UNet feed-forwards anywhere but OMGSR-S's bf16 tier."""
+    if isinstance(policy, dict) and isinstance(policy.get("unet"), dict) and "fp8_ff" in policy["unet"]:
+        raise ValueError(f"unet fp8_ff belongs to OMGSR-S's bf16 tier (weight_dtype=torch.bfloat16), not to {where}")
+
+
 def set_mx(model: nn.Module, patterns: Iterable[str]) -> int:
     """Move the both-sides split of the matching 3x3 stride-1 (halo-tile kernel) and 1x1 (MX GEMM kernel) convolutions (Cin % 64 == 0,
     >= 96 output channels) to the mixed-precision form (op_split 3); layers that do not qualify keep what they had. OMGSR_MX=0
