@@ -354,6 +354,153 @@ def split_rounded(y: torch.Tensor, dtype: torch.dtype):
     return hi, (y32 - hi.float()).to(dtype)
 
 
+# ---- GroupNorm statistics (tests/test_gn_stats_probes_*.py) --------------------------------------------------------------------------
+# Every producer keeps (sum, sum of squares) of the fp32 values it stores in fp32 partials - per lane, per wave, per 32-row block or per
+# pixel chunk - and the finalisers fold the partials in double. When every value of an (image, group) is an integer multiple of one quantum q
+# and the largest run of values one fp32 partial can cover (`slot_elems`) keeps sum |v| / q and sum v^2 / q^2 below 2^24, every partial sum is
+# an exact integer times q (q^2) in ANY summation order, so the folded partials equal the float64 sums below bit for bit.
+
+def stats_act(gen: torch.Generator, shape, img_e=(0, 1), mant=(1, 3)) -> torch.Tensor:
+    """Activations [N, ..., C] = +-m 2^(e[n]): ONE exponent per image (consecutive images alternate inside img_e, so a value credited to the
+    neighbouring image is off by a power of two) and none per channel, so the products of one output group share one quantum."""
+    N = shape[0]
+    e = img_e[0] + (torch.arange(N) + int(torch.randint(0, 2, (1,), generator=gen))) % (img_e[1] - img_e[0] + 1)
+    return signed_ints(gen, tuple(shape), *mant) * torch.exp2(e.float()).reshape(N, *([1] * (len(shape) - 1)))
+
+
+def group_exponents(gen: torch.Generator, groups: int, channels: int, span=(-2, 2)) -> torch.Tensor:
+    """[channels] exponents, one integer per group of channels / groups consecutive channels and none per channel inside a group; neighbouring
+    groups always differ (a channel credited to the group next door moves by a power of two, and one group keeps one quantum)."""
+    n = span[1] - span[0] + 1
+    assert n >= 2 and channels % groups == 0
+    return (span[0] + torch.randint(1, n, (groups,), generator=gen).cumsum(0) % n).float().repeat_interleave(channels // groups)
+
+
+def stats_wt(gen: torch.Generator, ce: torch.Tensor, cin: int, R: int = 3, S: int = 3, nnz: int = 2, mant=(1, 3), alt_sign: bool = False) -> torch.Tensor:
+    """[Cout, Cin, R, S]: +-m 2^(ce[output channel]) at nnz (tap, channel) positions per output channel, zero elsewhere. alt_sign: the sign
+    alternates with the output channel instead (for operands of one sign: the group's mean stays small against its spread)."""
+    cout = ce.numel()
+    v = signed_ints(gen, (cout, cin * R * S), *mant) * torch.exp2(ce)[:, None]
+    if alt_sign:
+        v = v.abs() * (1 - 2 * (torch.arange(cout) % 2).float())[:, None]
+    return (v * sparse_mask(gen, cout, cin * R * S, nnz)).reshape(cout, cin, R, S)
+
+
+def stats_bias(gen: torch.Generator, ce: torch.Tensor, img_e0: int = 0) -> torch.Tensor:
+    """An odd multiple (+-1, +-3) of HALF the finest product quantum 2^(ce + img_e0) per channel: every output is then an odd multiple of
+    q / 2 - never zero - so dropping or double-counting any single value changes the sum of squares."""
+    n = ce.numel()
+    return (torch.randint(0, 2, (n,), generator=gen).float() * 2 + 1) * (torch.randint(0, 2, (n,), generator=gen).float() * 2 - 1) * torch.exp2(ce + img_e0 - 1)
+
+
+def stats_residual(gen: torch.Generator, shape, ce: torch.Tensor, img_e0: int = 0) -> torch.Tensor:
+    """A residual [N, ..., C] of +-{1..3} whole product quanta 2^(ce + img_e0)."""
+    return signed_ints(gen, tuple(shape), 1, 3) * torch.exp2(ce + img_e0)
+
+
+def stats_values(gen: torch.Generator, shape, ce: torch.Tensor, img_e=(0, 1)) -> torch.Tensor:
+    """A tensor [N, P, C] for the statistics read pass: {1, 3} 2^(ce[channel] + e[image]) with the sign alternating over pixels and channels -
+    nonzero odd multiples of one quantum per (image, group), and a mean that stays below the spread even in a group of five values."""
+    N, P, C = shape
+    e = img_e[0] + (torch.arange(N) + int(torch.randint(0, 2, (1,), generator=gen))) % (img_e[1] - img_e[0] + 1)
+    odd = (torch.randint(0, 2, tuple(shape), generator=gen).float() * 2 + 1) * (1 - 2 * ((torch.arange(P)[:, None] + torch.arange(C)[None, :]) % 2).float())
+    return odd * torch.exp2(ce) * torch.exp2(e.float()).reshape(N, 1, 1)
+
+
+def group_sums(y: torch.Tensor, G: int):
+    """y [N, ..., C] exact values -> (S, Q) float64 [N, G]: sum and sum of squares per (image, group of C / G consecutive channels)."""
+    y = y.double()
+    N, C = y.shape[0], y.shape[-1]
+    v = y.reshape(N, -1, G, C // G)
+    return v.sum((1, 3)), (v * v).sum((1, 3))
+
+
+class StatsBudget:
+    """Asserted before a statistics probe launches: per (image, group) every value is a nonzero multiple of one quantum q (the finest of the
+    group), a normal fp32 value exactly representable in the stored type `dtype`, and the largest run of values one fp32 partial can cover
+    stays exact: max |v| slot_elems < 2^24 q and max v^2 slot_elems < 2^24 q^2 (the fold over slots is in double: no budget there, beyond the
+    2^53 the float64 reference itself needs)."""
+
+    def __init__(self, y: torch.Tensor, G: int, slot_elems: int, dtype: torch.dtype):
+        y = y.double()
+        N, C = y.shape[0], y.shape[-1]
+        assert C % G == 0
+        v = y.reshape(N, -1, G, C // G).permute(0, 2, 1, 3).reshape(N, G, -1)
+        self.nonzero = bool((v != 0).all())
+        self.stored = torch.equal(y.to(dtype).double(), y)
+        self.q = quantum(v).amin(-1)
+        self.amax = v.abs().amax(-1)
+        self.count = v.shape[-1]
+        self.slot_elems = min(int(slot_elems), self.count)
+        S, Q = v.sum(-1), (v * v).sum(-1)
+        m = S / self.count
+        self.m2, self.var = m * m, Q / self.count - m * m
+
+    def check(self) -> float:
+        assert self.nonzero, "a statistics probe must not hold an exactly-zero output: a dropped or doubled value could go unseen"
+        assert self.stored, "the exact output is not representable in the stored type: what is stored and what is summed would differ"
+        k = self.amax / self.q
+        worst = float((k * k * self.slot_elems).max())
+        assert worst < 2.0 ** 24 and float((k * self.slot_elems).max()) < 2.0 ** 24, \
+            f"statistics probe over its bit budget: max v^2 x slot = {worst:.3g} q^2 >= 2^24 (mixed quanta in a group, or too many bits)"
+        assert float((k * k * self.count).max()) < 2.0 ** 53, "the float64 reference would not be exact"
+        assert float(self.q.min()) ** 2 >= MIN_NORMAL and float(self.amax.max()) ** 2 * self.slot_elems < 2.0 ** 100, "values outside the normal fp32 range"
+        assert bool((self.m2 <= self.var).all()), "mean^2 > variance: the subtraction q / count - m^2 would amplify a last-bit difference"
+        return worst
+
+
+def finalize_ref(S: torch.Tensor, Q: torch.Tensor, count: float, eps: float):
+    """float64 restatement of gn_finalize_kernel: (mean, var, rstd) from the folded sums; eps enters as the fp32 value the kernel is handed."""
+    m = S.double() / float(count)
+    v = (Q.double() / float(count) - m * m).clamp(min=0.0)
+    eps32 = float(torch.tensor(eps, dtype=torch.float32))
+    return m, v, 1.0 / torch.sqrt(v + eps32)
+
+
+def merged_ref(parts, eps: float):
+    """float64 restatement of omgsr_groupnorm_finalize_merged (include/omgsr_hip.h): parts = [(S [T, N, G], Q, count, weight)] per tile-shape
+    group; mean = sum over (group, tile) of weight m, var = sum of weight max(q / count - m^2, 0), weight as the fp32 value the library holds."""
+    mm = vv = 0.0
+    for S, Q, count, weight in parts:
+        w32 = float(torch.tensor(weight, dtype=torch.float32))
+        m, v, _ = finalize_ref(S, Q, count, eps)
+        mm = mm + (w32 * m).sum(0)
+        vv = vv + (w32 * v).sum(0)
+    eps32 = float(torch.tensor(eps, dtype=torch.float32))
+    return mm, vv, 1.0 / torch.sqrt(vv + eps32)
+
+
+def fold_partials(partial: torch.Tensor, G: int):
+    """A producer's raw partials [N, nslot, entries, 2] -> (S, Q) float64 [N, G]: over the slots, and over the entries / G entries of a group."""
+    p = partial.double()
+    N, _, entries, _ = p.shape
+    assert entries % G == 0, f"{entries} entries do not fold into {G} groups"
+    f = p.sum(1).reshape(N, G, entries // G, 2).sum(2)
+    return f[..., 0], f[..., 1]
+
+
+def halo_partials_ref(y: torch.Tensor, G: int, per_channel: bool) -> torch.Tensor:
+    """What the halo-tile kernel's spatial form leaves for an exact output y [N, H, W, C] (igemm_halo_body.hip.h): float32
+    [N, 2 ceil(H / 8) ceil(W / 32), entries, 2], slot = (tile row-major, upper / lower four tile rows), entries = G or C. Pixels outside the
+    map add nothing. (The emulated partials of tests/test_gn_stats_probes_cpu.py's negative controls.)"""
+    N, H, W, C = y.shape
+    ty, tx = (H + 7) // 8, (W + 31) // 32
+    v = F.pad(y.double(), (0, 0, 0, tx * 32 - W, 0, ty * 8 - H)).reshape(N, ty, 2, 4, tx, 32, C)
+    s = torch.stack([v.sum((3, 5)), (v * v).sum((3, 5))], -1)                # [N, ty, wm, tx, C, 2]
+    s = s.permute(0, 1, 3, 2, 4, 5).reshape(N, ty * tx * 2, C, 2)
+    if not per_channel:
+        s = s.reshape(N, ty * tx * 2, G, C // G, 2).sum(3)
+    return s.float()
+
+
+def ulps32(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Distance in fp32 steps between two fp32 tensors of finite values."""
+    def ordered(t):
+        i = t.contiguous().view(torch.int32).long()
+        return torch.where(i < 0, -(i & 0x7FFFFFFF), i)
+    return (ordered(a) - ordered(b)).abs()
+
+
 # ---- the dispatcher's variant ids ----------------------------------------------------------------------------------------------------
 
 def variant_ids(source: str) -> set:

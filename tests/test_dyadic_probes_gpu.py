@@ -3,8 +3,9 @@ that ran and torch.equal against the float64 restatement of the packed bytes aft
 
 A rel-L2 bound on random data cannot see a defect confined to a few outputs (a correction chunk read from the wrong K block, a border tap
 lost, one ragged tile); with dyadic operands inside the bit budget every such defect changes the result. Routing comes from the shapes alone
-(the OMGSR_* A/B knobs are read once per process). Nonlinear epilogues (SiLU, GELU, GEGLU) and the GroupNorm-fused variants 10 / 11 stay
-with the tolerance tests."""
+(the OMGSR_* A/B knobs are read once per process). Nonlinear epilogues (SiLU, GELU, GEGLU) stay with the tolerance tests; the GroupNorm-fused
+variants 10 / 11, whose producer always applies SiLU, are probed on data where that SiLU is the identity in fp32 (gn_fused_case).
+tests/test_gn_stats_probes_gpu.py pins the GroupNorm statistics the same kernels' epilogues leave."""
 import os
 import sys
 
@@ -24,7 +25,8 @@ class _DryRun(Exception):
 
 
 def _launch(variant, fn):
-    """Run fn() with the per-launch timing on and assert that every omgsr_igemm launch it made was kernel variant `variant`."""
+    """Run fn() with the per-launch timing on and assert that every omgsr_igemm launch it made was kernel variant `variant` (None: that it made
+    no such launch - statistics kernels only; a tuple: ONE variant of these - a probe that pins what several GEMM-shaped kernels share)."""
     from omgsr_amd import _lib
     lib = _lib.load()
     torch.cuda.synchronize()
@@ -38,7 +40,10 @@ def _launch(variant, fn):
         lib.omgsr_timing_enable(0)
     ran = sorted({e.variant for e in buf[:n] if e.kind == 1})
     print(f"variant ran: {ran}")
-    assert ran == [variant], f"expected kernel variant {variant}, the dispatcher ran {ran}"
+    if isinstance(variant, tuple):
+        assert len(ran) == 1 and ran[0] in variant, f"expected one kernel variant of {variant}, the dispatcher ran {ran}"
+    else:
+        assert ran == ([] if variant is None else [variant]), f"expected kernel variant {variant}, the dispatcher ran {ran}"
     return out
 
 
@@ -423,6 +428,60 @@ def v8_multi_phase_mx(dev, launch):
     _multi(dev, launch, 8, [(2, 32, 40), (1, 32, 32)], 128, 128, "mx", True, 802)
 
 
+# ---- variants 10 / 11: the GroupNorm-fused halo producer --------------------------------------------------------------------------------------
+
+def gn_fused_case(dev, groups, nimg, seed, Cin=32, Cout=128, G=32):
+    """Operands of a conv whose patch producer normalises: stream tensors x_k [n_k, h_k, w_k, Cin] = +-{1..3}, a dyadic (scale, shift) table
+    [nimg, Cin, 2] (scale 2^(image % 2), shift 40 or 44 by channel parity; row n uses image n % nimg) and a weight of one +-2^e tap per output
+    whose sign alternates with the output channel. SiLU is the one activation the producer has (omgsr_igemm refuses any other gn_act); every
+    normalised value x scale + shift lies in 34 .. 50, where silu_f is the identity in fp32: exp(-v) < 2^-46, so 1.0f + exp(-v) is 1.0f, its
+    v_rcp_f32 is 1.0f and v * 1.0f is v. The values are integers below 2^6: exact in the compute type the producer rounds to. The shift is
+    nonzero, so a border tap that picked up `shift` instead of the zero padding of the NORMALISED map would change the result.
+    Returns (xs, pw, make_spec, exact outputs float64 before the output rounding, G); make_spec() is a fresh GnSpec carrying the table."""
+    ops = _ops()
+    g = _g(seed)
+    ce = dp.group_exponents(g, G, Cout)
+    pw = ops.pack_conv_weight(dp.stats_wt(g, ce, Cin, 3, 3, 1, (1, 1), alt_sign=True), dp.stats_bias(g, ce), device=dev)
+    table = torch.empty(nimg, Cin, 2)
+    table[..., 0] = torch.exp2((torch.arange(nimg) % 2).float())[:, None]
+    table[..., 1] = (40.0 + 4.0 * (torch.arange(Cin) % 2).float())[None, :]
+    xs, exacts = [], []
+    for n, h, w in groups:
+        x = dp.stats_act(g, (n, h, w, Cin), img_e=(0, 0))
+        t = table[torch.arange(n) % nimg][:, None, None]                     # [n, 1, 1, Cin, 2]
+        a = x * t[..., 0] + t[..., 1]
+        assert float(a.min()) >= 32.0 and torch.equal(a.to(ops.act_dtype()).float(), a)
+        exacts.append(dp.conv_ref(a.to(dev, ops.act_dtype()), pw, bias=pw.bias))
+        xs.append(x.to(dev, ops.stream_dtype()))
+    table = table.to(dev)
+
+    def make_spec():
+        stat = torch.zeros(nimg, G, device=dev)
+        spec = ops.GnSpec(stat, stat + 1.0, None, None, G, ops.ACT_SILU)
+        spec._table = table
+        return spec
+    return xs, pw, make_spec, exacts, G
+
+
+def v10_gn_fused_identity_silu(dev, launch):
+    """bf16; GroupNorm apply as the halo kernel's patch producer: four rows sharing two images' (scale, shift), 96 x 160 maps, 32 -> 128 (240
+    tiles), on data where its SiLU is the identity (gn_fused_case): x * scale + shift, the rounding to the compute type and the zero padding of the
+    normalised map are exact."""
+    ops = _ops()
+    xs, pw, spec, exacts, _ = gn_fused_case(dev, [(4, 96, 160)], 2, 1001)
+    y = launch(10, lambda: ops.conv2d(xs[0], pw, pad=1, gn=spec()))
+    _eq(y, dp.rounded(exacts[0], ops.stream_dtype()), "GroupNorm-fused conv")
+
+
+def v11_gn_fused_multi_identity_silu(dev, launch):
+    """bf16; the same producer in a launch group: two tile shapes (120 + 96 tiles), rows of both sharing two images' table."""
+    ops = _ops()
+    xs, pw, spec, exacts, _ = gn_fused_case(dev, [(2, 96, 160), (2, 96, 128)], 2, 1101)
+    ys = launch(11, lambda: ops.conv2d_multi(xs, pw, pad=1, gn=spec()))
+    for y, want in zip(ys, exacts):
+        _eq(y, dp.rounded(want, ops.stream_dtype()), "GroupNorm-fused launch group member")
+
+
 # ---- variant 12: halo split-K (MX fp8) -------------------------------------------------------------------------------------------------
 
 def v12_halo_splitk_mx(dev, launch):
@@ -597,6 +656,8 @@ PROBES = {
     "v8_multi_phase_bf16": ("bf16", v8_multi_phase_bf16),
     "v8_multi_phase_mx": ("fp32", v8_multi_phase_mx),
     "v9_gmx_mx_operand": ("fp32", v9_gmx_mx_operand),
+    "v10_gn_fused_identity_silu": ("bf16", v10_gn_fused_identity_silu),
+    "v11_gn_fused_multi_identity_silu": ("bf16", v11_gn_fused_multi_identity_silu),
     "v12_halo_splitk_mx": ("fp32", v12_halo_splitk_mx),
     "v13_mx6_single": ("fp32", v13_mx6_single),
     "v14_mx6_multi": ("fp32", v14_mx6_multi),
