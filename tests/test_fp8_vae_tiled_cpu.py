@@ -55,8 +55,24 @@ def test_variant_22_is_assigned_in_conv_mxfp8_only():
     own = open(os.path.join(ROOT, "omgsr_amd", "csrc", "conv_mxfp8.hip")).read()
     assert re.search(rf"ts\.rec\.variant = {VARIANT};", own) and re.search(r"ts\.rec\.variant = 21;", own) and "OMGSR_TK_IGEMM" in own
     assert len(re.findall(r"__global__[^\n]*\bmxfp8_conv_kernel\(", own)) == 1 and len(re.findall(r"__global__[^\n]*\bmxfp8_conv_multi_kernel\(", own)) == 1
-    # both kernels are the shared body after the lookup
-    assert len(re.findall(r"\bmxfp8_conv_body\(", own)) == 3
+    # both kernels are the shared body after the lookup: each __global__ calls the <9, false> instantiation of the one tile body, and nothing else does
+    assert re.findall(r"\bmxfp8_conv_tile<([^>]*)>\(", own) == ["9, false", "9, false"] and "mxfp8_conv_body" not in own
+    for kernel in ("mxfp8_conv_kernel", "mxfp8_conv_multi_kernel"):
+        body = own[own.index(f"void {kernel}("):].split("\n}\n")[0]
+        assert len(re.findall(r"\bmxfp8_conv_tile<9, false>\(", body)) == 1, kernel
+
+
+def test_the_three_units_share_one_tile_body():
+    """Where the one body lives: conv_mxfp8_body.hip.h holds the scaled-MFMA statement, the three units include it and hold none of their own."""
+    csrc = os.path.join(ROOT, "omgsr_amd", "csrc")
+    mfma = "v_mfma_scale_f32_32x32x64_f8f6f4"
+    body = open(os.path.join(csrc, "conv_mxfp8_body.hip.h")).read()
+    assert len(re.findall(rf'asm volatile\("[^"]*{mfma}', body)) == 1
+    assert re.search(r"static_assert\(!\(WINDOWED && TAPS == 4\)", body)
+    for unit, inst in (("conv_mxfp8.hip", "9, false"), ("conv_mxfp8_up.hip", "4, false"), ("conv_mxfp8_deep.hip", "9, true")):
+        src = open(os.path.join(csrc, unit)).read()
+        assert '#include "conv_mxfp8_body.hip.h"' in src and mfma not in src, unit
+        assert set(re.findall(r"\bmxfp8_conv_tile<([^>]*)>\(", src)) == {inst}, unit
 
 
 def test_symbols_are_additive_under_abi_v22():

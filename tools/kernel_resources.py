@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, HERE)
 from omgsr_amd.build import kernel_resources  # noqa: E402
 
-PINNED_PREFIXES = ("igemm_", "attn_kernel", "splitk_reduce")
+PINNED_PREFIXES = ("igemm_", "attn_kernel", "splitk_reduce", "mxfp8_conv")
 GOLDEN = os.path.join(HERE, "tests", "golden", "kernel_resources.json")
 
 
